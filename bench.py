@@ -4,6 +4,19 @@ elasticity path (BASELINE.json config 2: 1M hex8 per GPU, K and r assembled) on 
     python bench.py [--gpus N] [--steps K] [--warmup W]      (N > 1: starts its N ranks itself)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N   (one rank per GPU)
 
+A plain run does what the headline figure needs and nothing else: set-up, the warm-up (RAMP_STEPS
+untimed steps that bring the GPU to its working clocks, then the W steps asked for), the K
+timed steps, one JSON result line (metric, value, unit, higher_is_better, dtype, ms_per_step, the
+configuration).  `--full` adds everything else the benchmark measures: the on-box peaks and the
+roofline of the headline kernel (hipEvent passes, rocprofv3 counter passes), the per-rank phases,
+the CPU baselines and the secondary lines of the other BASELINE configurations; the `--no-*`,
+`--only-primary`, `--peaks-after`, `--timing-after` and `--pmc-json` options select among those
+and mean nothing without `--full`.
+`--dump-outputs DIR` writes what the last timed step computed (the residual f and the tangent
+values K the caller of evaluate receives) as DIR/<name>.npy, float64, at most 64 MB in all: f
+whole and a fixed, seeded sample of K's values at 1M elements (see dump_outputs).  Mesh, u and
+the sample are seeded, so two builds run with the same arguments can be compared array by array.
+
 Without WORLD_SIZE in the environment, `--gpus N` (N > 1) starts N rank processes of this script
 (tools/rank_launcher.py: RANK / LOCAL_RANK / WORLD_SIZE / MASTER_*, before torch is imported, no
 exec) and exits with the first failing rank's code; under a launcher WORLD_SIZE must equal N.
@@ -893,11 +906,48 @@ def totlag_sweep_secondary(dev, n, steps, with_pmc):
         return {"workload": "hex8-totlag structured (sweep)", "error": repr(e)}
 
 
+DUMP_BUDGET_BYTES = 60 * 10**6   # all ranks' arrays together, under the 64 MB a dump may take
+DUMP_SEED = 20251015
+RAMP_STEPS = 500                 # a plain run's untimed steps in front of its --warmup steps
+
+
+def _dump_sample(n, max_entries):
+    """Positions of an n-vector that a dump keeps: all of them if they fit, else a fixed sample
+    (sorted, without repeats, drawn from DUMP_SEED and n alone)."""
+    if n <= max_entries:
+        return None
+    rng = np.random.default_rng([DUMP_SEED, n])
+    return np.unique(rng.integers(0, n, size=max_entries))
+
+
+def dump_outputs(path, f, K, rank, world):
+    """Writes the arrays the last timed evaluate returned to its caller -- the residual f and the
+    tangent's CSR values K of this rank's owned rows -- as float64 .npy files under `path`:
+    f.npy, K.npy (f_rankR.npy, K_rankR.npy with more than one rank).  Each rank may write
+    DUMP_BUDGET_BYTES / ranks: f takes up to half of that, K the rest; an array that does not fit
+    is written at the positions of _dump_sample (K of the 1M-element box: 4.4M of 245M values)."""
+    os.makedirs(path, exist_ok=True)
+    budget = DUMP_BUDGET_BYTES // world // 8
+    suffix = f"_rank{rank}" if world > 1 else ""
+    left = budget
+    for name, t, share in (("f", f, budget // 2), ("K", K, None)):
+        idx = _dump_sample(t.numel(), share if share is not None else left)
+        a = t if idx is None else t[torch.from_numpy(idx).to(t.device)]
+        a = np.ascontiguousarray(a.cpu().numpy(), dtype=np.float64)
+        left -= a.size
+        np.save(os.path.join(path, f"{name}{suffix}.npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=30)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline line: measured peaks, kernel-time and counter passes "
+                         "(roofline), per-rank phases, CPU baselines and the secondary lines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write f and (a seeded sample of) K of the last timed step as DIR/*.npy")
     ap.add_argument("--elems-per-dir", dest="n", type=int, default=100,
                     help="elements per direction per GPU")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -1025,7 +1075,7 @@ def main():
     # GPU before its warm-up, so that the timed steps start on a GPU already at its working
     # clocks (the reported peaks are rank 0's)
     peaks = None
-    if not args.peaks_after:
+    if args.full and not args.peaks_after:
         try:
             peaks = fcg.measure_peaks(dev.index) + fcg.measure_hbm(dev.index)
         except Exception as e:  # report, never hide
@@ -1049,7 +1099,18 @@ def main():
     # working clocks (measured: with 5 warm-up steps alone the 20 timed steps average 1.07 ms,
     # with this pass in front 1.03 ms, at an unchanged warm kernel time); its kernel times are
     # reported as ms_kernel_cold, the roofline uses the pass after the timed steps
-    cold = kernel_timing_pass() if args.timing_before else None
+    cold = kernel_timing_pass() if args.full and args.timing_before else None
+    if not args.full:
+        # a plain run has neither the peak measurement nor the hipEvent pass in front of its
+        # warm-up, so its warm-up starts with RAMP_STEPS untimed steps (half a second at 1M
+        # elements per GPU) that bring the GPU to the same working clocks: measured with
+        # --steps 20 --warmup 5, alternated on one GPU, 1.00-1.01 ms per step without them and
+        # 0.927-0.930 ms with them against 0.934-0.954 ms of --full --only-primary (0.922 vs
+        # 0.921 ms at --steps 200 --warmup 30)
+        for _ in range(RAMP_STEPS):
+            step(norm=False)
+        ev.check_error()
+        torch.cuda.synchronize(dev)
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize(dev)
@@ -1068,6 +1129,47 @@ def main():
     if world > 1:
         dist.barrier()
     t1 = time.perf_counter()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, f, K, rank, world)
+    if not args.full:
+        # the headline line alone: nothing but the window above is measured
+        elapsed = _ctl_max(t1 - t0, world)
+        if rank == 0:
+            print(json.dumps({
+                "metric": "element-evaluations/sec (hex8 linear elasticity, K+r global assembly)",
+                "value": mesh.n_ele_global / (elapsed / args.steps),
+                "unit": "element-evaluations/s",
+                "n_gpus": world,
+                "steps": args.steps,
+                "warmup": args.warmup,
+                "ms_per_step": 1e3 * elapsed / args.steps,
+                "higher_is_better": True,
+                "scaling": "weak",
+                "vs_baseline": None,
+                "dtype": "f64",
+                "data": "synthetic (GridGenerator box, jitter 0.1h, analytic displacement field)",
+                "config": {
+                    "workload": f"hex8-linear-{args.n}^3-per-gpu",
+                    "global_intervals": list(iv),
+                    "elements_global": mesh.n_ele_global,
+                    "elements_evaluated_per_gpu": mesh.n_ele,
+                    "dofs_owned_rank0": mesh.n_rows,
+                    "nnz_rank0": mesh.nnz,
+                    "path": "structured" if ev.info.path == fcg.PATH_STRUCTURED else int(ev.info.path),
+                    "setup_s_rank0": t_setup,
+                },
+                "untimed_steps_before_timed": RAMP_STEPS + args.warmup,
+                "outputs_dumped_to": args.dump_outputs,
+                "full": False,
+            }))
+        if imp is not None:
+            imp.close()
+        ev.close()
+        if comm is not None:
+            comm.close()
+        if world > 1:
+            dist.destroy_process_group()
+        return
     nrm = step()
     t_el, t_as = kernel_timing_pass()
     phases = phase_pass(max(3, min(args.steps, 10)))
