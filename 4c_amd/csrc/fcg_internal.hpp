@@ -15,10 +15,9 @@ namespace fcg {
 // Per-incidence scratch record written by the element kernel and consumed by the row-assembly
 // kernel: the element's block-row of node a (3 rows x 3*npe columns, b-major) then f_a (3).
 // One owned incidence's block row (3 x 3 npe) and its 3 residual entries.  hex27: padded to
-// FCG_REC27 = 256 doubles so that records start on 128-byte lines: no line is shared by two
-// records, which the overlapped schedule needs (a row node on another XCD reads its records
-// while a neighbouring record's element may not have run yet; a shared line could then sit stale
-// in that XCD's L2).  Unpadded (246) measured the same (profiles/r06/r06_h27_record_store_ab.txt).
+// FCG_REC27 = 256 doubles so that records start on 128-byte lines.  Unpadded (246) measured the
+// same (profiles/r06/r06_h27_record_store_ab.txt); shrinking it changes scratch_bytes and the
+// memory the context takes, so that is a change of its own.
 #ifndef FCG_REC27
 #define FCG_REC27 256
 #endif
@@ -73,9 +72,9 @@ struct DeviceMesh {
   int32_t* rec_ele = nullptr;       // [n_rec][8] element of each slot, -1 = empty
   uint8_t* rec_a = nullptr;         // [n_rec][8] local node of the row node in the slot's element
   uint32_t* rec_tmap = nullptr;     // [n_rec][32] per column triple: slot s's element node in nibble s (8 = none)
-  // hex27 StVK general path (fcg_hex27.hip): per-element symmetric records in `scratch`
+  // hex27 StVK general path (fcg_hex27.hip): the matrix-core element kernel writes the incidence
+  // records in `scratch`, assemble27_kernel sums them
   bool h27s = false;
-  bool h27_increc = false;  // hex27 element kernel writes incidence block rows (assemble27_kernel)
   int32_t* inc_ele = nullptr;       // [n_inc] element of each incidence
   uint8_t* inc_a = nullptr;         // [n_inc] local node of the row node in that element
   int32_t* asm_order = nullptr;     // [n_rownodes] row nodes in Morton order of their coordinates
@@ -97,19 +96,6 @@ struct DeviceMesh {
   int32_t* h27_rows = nullptr;       // [n_rownodes] row nodes by completing slab, then Morton order
   int32_t* h27_rslot0 = nullptr;     // [n_rownodes] ring slot of the row node's first record
   int32_t* h27_slot = nullptr;       // [n_ele][27] ring slot of incidence (e, a), -1 = not owned
-  // hex27 overlapped schedule (FCG_H27_OVERLAP=1 with the full scratch; measured slower than the
-  // element launch + row-assembly launch): one queue of element chunks (ovl_chunk
-  // consecutive elements) and row items (runs of row nodes whose incident elements all lie in
-  // completed bands of ovl_band_chunks chunks)
-  bool h27_ovl = false;
-  int64_t ovl_items = 0, ovl_chunk = 0, ovl_nchunks = 0, ovl_nbands = 0;
-  int ovl_band_chunks = 1;
-  int32_t* ovl_queue = nullptr;     // [ovl_items] chunk c >= 0 | ~row item
-  int32_t* ovl_ritem = nullptr;     // [row items][4] rows [j0, j1) of ovl_rows, bands [lo, hi]
-  int32_t* ovl_rows = nullptr;      // [n_rownodes] by completing band, then Morton order
-  int64_t* ovl_rmeta = nullptr;     // [n_rownodes][4] of ovl_rows[j]: CSR offset, first row,
-                                    // first incidence, row length | incidences << 16
-  unsigned* ovl_sync = nullptr;     // [1 + ovl_nbands] claim counter, completed chunks per band
 
   // structured (row-block sweep) plan, hex8 only
   int path = FCG_PATH_GENERAL;
@@ -189,20 +175,15 @@ hipError_t launch_element_colored(const DeviceMesh& m, const double* d_u_col, bo
     bool overwrite, double* d_K, double* d_fint, hipStream_t stream);
 hipError_t launch_assemble(const DeviceMesh& m, bool want_k, bool overwrite, double* d_K,
     double* d_fint, hipStream_t stream);
-// hex27 StVK on any mesh (fcg_hex27.hip): element kernel writing one symmetric record per
-// element (blocks a <= b + f_e), then one wavefront per owned row node in Morton order.
+// hex27 StVK on any mesh (fcg_hex27.hip): the element kernel writes one record per owned
+// incidence (its 3 x 81 block row + f_a) for elements [e_begin, e_end) (e_end < 0: all), which
+// launch_assemble (assemble27_kernel) sums per owned row node.
 void upload_h27_tables();
-constexpr int64_t kH27RecDoubles = 378 * 9 + 81 + 1;  // even: 16-byte aligned records
 hipError_t launch_h27_element(const DeviceMesh& m, const double* d_u_col, bool want_k,
     hipStream_t stream, int64_t e_begin = 0, int64_t e_end = -1);
 // hex27 slab schedule: the row assembly of the row nodes completed by slab s
 hipError_t launch_assemble27_slab(const DeviceMesh& m, int64_t s, bool want_k, bool overwrite,
     double* d_K, double* d_fint, hipStream_t stream);
-hipError_t launch_h27_assemble(const DeviceMesh& m, bool want_k, bool overwrite, double* d_K,
-    double* d_fint, hipStream_t stream);
-// hex27 overlapped schedule: element chunks and row items of one queue in one launch
-hipError_t launch_h27_overlap(const DeviceMesh& m, const double* d_u_col, bool want_k,
-    bool overwrite, double* d_K, double* d_fint, hipStream_t stream);
 // hex27 StVK on a verified lattice: the same element kernel adding its blocks straight into the
 // CSR rows, four colour launches of pencils (runs of elements along x, one workgroup each)
 hipError_t launch_h27_pencil(const DeviceMesh& m, const double* d_u_col, bool want_k,

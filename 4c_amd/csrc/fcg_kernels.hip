@@ -3,8 +3,11 @@
 //  element_kernel   Discretization::evaluate's column-element loop + SolidEleCalc's Gauss-point
 //                   loop (4C_fem_discretization_evaluate.cpp:83-102,
 //                   4C_solid_3D_ele_calc.cpp:110-240): gathers X and u, checks the nodal Jacobian
-//                   determinants, evaluates J^-1, N_XYZ, strains, StVK stresses, f_e and K_e, and
-//                   writes every owned block-row of K_e plus f_a into an incidence-ordered scratch.
+//                   determinants, evaluates J^-1, N_XYZ, F, strains, the ElastHyper/CoupNeoHooke
+//                   stresses and cmat, f_e and K_e, and writes every owned block-row of K_e plus
+//                   f_a into an incidence-ordered scratch (or, colour-ordered, into the CSR rows).
+//  element_kernel_h8  the same loop for hex8 StVK, 8 lanes per element (fcg_hex8_element.hpp);
+//                   hex27 StVK has its own kernels in fcg_hex27.hip.
 //  assemble_kernel  SparseMatrix::assemble + LinAlg::assemble(Vector) for owned rows
 //                   (4C_linalg_sparsematrix.cpp:444-576, 4C_linalg_utils_sparse_algebra_assemble.cpp:72-92)
 //                   as a deterministic gather: one wavefront per owned row node sums the block-rows
@@ -178,30 +181,28 @@ __device__ inline void jacobian(const double* __restrict__ dN, const double* __r
   }
 }
 
-template <int NPE, int KIN, int MAT = 0>
+// LDS of element_kernel (TotLag, ElastHyper/CoupNeoHooke: the only users left, enforced at create)
+template <int NPE>
 struct ElementShared {
   static constexpr int NGP = NPE;
   double X[3 * NPE];
   double U[3 * NPE];
   union {
     struct {
-      double NX[NGP * NPE * 3];           // [g][c][d]
-      double P[KIN ? NGP * NPE * 3 : 1];  // F * N_XYZ_c  (TotLag)
+      double NX[NGP * NPE * 3];  // [g][c][d]
+      double P[NGP * NPE * 3];   // F * N_XYZ_c
     };
-    // TotLag hex27, colour-ordered path: the element's blocks a <= b (c_pairs27 order, 3 x 3
+    // hex27, colour-ordered path: the element's blocks a <= b (c_pairs27 order, 3 x 3
     // column-major), written once N_XYZ and P are no longer read
-    double KSu[(NPE == 27 && KIN) ? 378 * 9 : 1];
+    double KS[NPE == 27 ? 378 * 9 : 1];
   };
-  // linear hex27: the same image in its own space (24 + 27 KB still allow 3 workgroups per CU),
-  // written by the pair threads directly
-  double KSs[(NPE == 27 && !KIN) ? 378 * 9 : 1];
-  __device__ double* ks() { return KIN ? KSu : KSs; }
+  double unused8;                         // keeps the offsets below (and the kernels' code) as they were
   double invJ[NGP * 9];
   double fac[NGP];
   double S[NGP * 6];                      // PK2 stress, Voigt xx yy zz xy yz zx
-  double F[KIN ? NGP * 9 : 1];
-  double M[KIN ? NGP * 6 : 1];            // F F^T (sym)
-  double Cm[MAT ? NGP * 36 : 1];          // ElastHyper: cmat (column-major 6x6) per Gauss point
+  double F[NGP * 9];
+  double M[NGP * 6];                      // F F^T (sym)
+  double Cm[NGP * 36];                    // ElastHyper: cmat (column-major 6x6) per Gauss point
   int bad;
   // colour-ordered direct assembly: per local node its incidence (-1 = row not owned), the CSR
   // offset and length of its rows, and the column position of every element node in them
@@ -324,7 +325,6 @@ struct ElementArgs {
   const int64_t* rowptr;
   double* K;
   double* fint;
-  int mfma;  // hex27 StVK: node-pair blocks on v_mfma_f64_16x16x4_f64 (else the VALU pair loop)
 };
 
 // Colour-ordered direct assembly: is element e (first-touch bits ft, see build_colored_plan in
@@ -344,123 +344,20 @@ __device__ inline bool first_touch27(const uint8_t* loc, uint32_t ft, int a, int
   return first;
 }
 
-// hex27 StVK node-pair blocks on the FP64 matrix cores (v_mfma_f64_16x16x4_f64).  With the rows
-// (a, i) of the element's 81 DOFs ordered i-major and each node range padded to 32,
-//   X_ij[a][b] = sum_g fac_g Q_g[a][i] Q_g[b][j]       (Q = N_XYZ linear, F N_XYZ TotLag)
-// is 9 tiles of 16 x 16 per (a-range, b-range) pair over K = 27 Gauss points (7 steps of 4), and
-// because the f64 MFMA's output layout depends only on the position in the tile, one lane holds
-// X_ij and X_ji of the same (a, b) for all i, j: K_ab[i][j] = lambda X_ij + mu X_ji + ... is formed
-// in registers.  TotLag adds mu H_ij + delta_ij geo = sum over (g, k) of N_a,k times
-// fac (mu (F F^T)_ij N_b,k + delta_ij (S N_b)_k) -- 6 more tiles over K = 81 (21 steps).  Waves
-// 0..2 take the (a, b) ranges (0,0), (0,1), (1,1) (a <= b is all the image needs); the blocks go to
-// the LDS image KS (which TotLag aliases with N_XYZ / P: written after a barrier).
-typedef double f64x4_t __attribute__((ext_vector_type(4)));
-template <int KIN, typename SH>
-__device__ inline void pair_phase_mfma27(SH& sh, double* KS, double lam, double mu, int tid)
-{
-  const int wave = tid >> 6, lane = tid & 63;
-  const int at = wave == 2 ? 1 : 0, bt = wave == 0 ? 0 : 1;
-  const int r16 = lane & 15, kq = lane >> 4;
-  const int a_l = 16 * at + r16, b_l = 16 * bt + r16;
-  const bool va = a_l < 27, vb = b_l < 27;
-  const int a_c = va ? a_l : 0, b_c = vb ? b_l : 0;  // clamped: no read past the node range
-  f64x4_t X[9], H[6];
-#pragma unroll
-  for (int q = 0; q < 9; ++q) X[q] = f64x4_t{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-  for (int q = 0; q < 6; ++q) H[q] = f64x4_t{0.0, 0.0, 0.0, 0.0};
-  if (wave < 3)
-  {
-    const double* Q = KIN ? sh.P : sh.NX;  // [g][node][d]
-#pragma unroll
-    for (int st = 0; st < 7; ++st)
-    {
-      const int g = 4 * st + kq;
-      const bool vg = g < 27;
-      const int gc = vg ? g : 0;
-      const double fg = vg ? sh.fac[gc] : 0.0;
-      double av[3], bv[3];
-#pragma unroll
-      for (int i = 0; i < 3; ++i)
-      {
-        av[i] = va ? fg * Q[3 * (27 * gc + a_c) + i] : 0.0;
-        bv[i] = (vg && vb) ? Q[3 * (27 * gc + b_c) + i] : 0.0;
-      }
-#pragma unroll
-      for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-          X[3 * i + j] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[i], bv[j], X[3 * i + j], 0, 0, 0);
-    }
-    if constexpr (KIN == 1)
-    {
-      for (int st = 0; st < 21; ++st)
-      {
-        const int kk = 4 * st + kq;
-        const bool vk = kk < 81;
-        const int g = vk ? kk / 3 : 0, k = vk ? kk - 3 * (kk / 3) : 0;
-        const double fg = vk ? sh.fac[g] : 0.0;
-        const double an = va ? sh.NX[3 * (27 * g + a_c) + k] : 0.0;
-        const double* nb = sh.NX + 3 * (27 * g + b_c);
-        const double n0 = vb ? nb[0] : 0.0, n1 = vb ? nb[1] : 0.0, n2 = vb ? nb[2] : 0.0;
-        const double* S = sh.S + 6 * g;
-        const double* M = sh.M + 6 * g;
-        const double nk = k == 0 ? n0 : (k == 1 ? n1 : n2);
-        const double snk = k == 0 ? S[0] * n0 + S[3] * n1 + S[5] * n2
-                                  : (k == 1 ? S[3] * n0 + S[1] * n1 + S[4] * n2
-                                            : S[5] * n0 + S[4] * n1 + S[2] * n2);
-        const double fs = fg * snk, fm = fg * mu * nk;
-        H[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(an, fs + fm * M[0], H[0], 0, 0, 0);
-        H[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(an, fs + fm * M[1], H[1], 0, 0, 0);
-        H[2] = __builtin_amdgcn_mfma_f64_16x16x4f64(an, fs + fm * M[2], H[2], 0, 0, 0);
-        H[3] = __builtin_amdgcn_mfma_f64_16x16x4f64(an, fm * M[3], H[3], 0, 0, 0);
-        H[4] = __builtin_amdgcn_mfma_f64_16x16x4f64(an, fm * M[4], H[4], 0, 0, 0);
-        H[5] = __builtin_amdgcn_mfma_f64_16x16x4f64(an, fm * M[5], H[5], 0, 0, 0);
-      }
-    }
-  }
-  __syncthreads();  // TotLag: KS aliases N_XYZ / P
-  if (wave < 3)
-  {
-    const int b = 16 * bt + r16;
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-    {
-      const int a = 16 * at + kq + 4 * r;
-      if (a < 27 && b < 27 && a <= b)
-      {
-        const int pidx = 27 * a - (a * (a - 1)) / 2 + b - a;
-        double* K = KS + 9 * pidx;
-        const double tr = mu * (X[0][r] + X[4][r] + X[8][r]);
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-          for (int j = 0; j < 3; ++j)
-          {
-            double v = lam * X[3 * i + j][r] + mu * X[3 * j + i][r];
-            if constexpr (KIN == 0)
-              v += i == j ? tr : 0.0;
-            else
-              v += i == j ? H[i][r] : H[(i + j == 1) ? 3 : ((i + j == 3) ? 4 : 5)][r];
-            K[i + 3 * j] = v;
-          }
-      }
-    }
-  }
-}
-
 // ---------------------------------------------------------------------------------- element
 // ASM: 0 = block rows into the incidence scratch (general path, assemble_kernel sums them);
 // 1 / 2 = colour-ordered direct assembly, ACCUMULATE / OVERWRITE (hex27 lattice path).
-template <int NPE, int KIN, int BLOCK, int MAT = 0, int ASM = 0>
-__global__ __launch_bounds__(BLOCK, (NPE == 27 && MAT == 0) ? 3 : 1) void element_kernel(ElementArgs A)
+// Total Lagrangean kinematics with ElastHyper/CoupNeoHooke only (fcg_create enforces the pairing);
+// StVK runs in element_kernel_h8 and fcg_hex27.hip.
+template <int NPE, int BLOCK, int ASM = 0>
+__global__ __launch_bounds__(BLOCK, 1) void element_kernel(ElementArgs A)
 {
   constexpr int NGP = NPE;
   constexpr bool SYM = (NPE == 27);             // hex27: compute a<=b and mirror
   constexpr int NPAIR = SYM ? NPE * (NPE + 1) / 2 : NPE * NPE;
   constexpr int REC = int(record_doubles(NPE));
   constexpr int ROWLEN = 3 * NPE;
-  __shared__ ElementShared<NPE, KIN, MAT> sh;
+  __shared__ ElementShared<NPE> sh;
   const int tid = threadIdx.x;
   const double* dNgp = Tables<NPE>::dNgp();
   const double* dNnode = Tables<NPE>::dNnode();
@@ -645,125 +542,92 @@ __global__ __launch_bounds__(BLOCK, (NPE == 27 && MAT == 0) ? 3 : 1) void elemen
     __syncthreads();
     EL_STAMP(2);
 
-    // 4. strains and StVK stress per Gauss point
+    // 4. deformation gradient, strains, stress and cmat per Gauss point
     if (tid < NGP)
     {
       const int g = tid;
       const double* NX = sh.NX + 3 * NPE * g;
       double E[6];
-      if (KIN == 0)
+      // evaluate_deformation_gradient (calc_lib.hpp:579-605): hex8 from current coordinates,
+      // hex27 as I + u N_XYZ^T.  F(i,j) column-major.
+      double F[9];
+      for (int k = 0; k < 9; ++k) F[k] = 0.0;
+      for (int c = 0; c < NPE; ++c)
       {
-        // evaluate_linear_strain_gradient + evaluate_linear_gl_strain (calc_lib.hpp:682-799)
-        for (int k = 0; k < 6; ++k) E[k] = 0.0;
-        for (int c = 0; c < NPE; ++c)
-        {
-          const double n0 = NX[3 * c], n1 = NX[3 * c + 1], n2 = NX[3 * c + 2];
-          const double u0 = sh.U[3 * c], u1 = sh.U[3 * c + 1], u2 = sh.U[3 * c + 2];
-          E[0] += n0 * u0;
-          E[1] += n1 * u1;
-          E[2] += n2 * u2;
-          E[3] += n1 * u0 + n0 * u1;
-          E[4] += n2 * u1 + n1 * u2;
-          E[5] += n2 * u0 + n0 * u2;
-        }
-      }
-      else
-      {
-        // evaluate_deformation_gradient (calc_lib.hpp:579-605): hex8 from current coordinates,
-        // hex27 as I + u N_XYZ^T.  F(i,j) column-major.
-        double F[9];
-        for (int k = 0; k < 9; ++k) F[k] = 0.0;
-        for (int c = 0; c < NPE; ++c)
-        {
-          const double n0 = NX[3 * c], n1 = NX[3 * c + 1], n2 = NX[3 * c + 2];
-          double q[3];
+        const double n0 = NX[3 * c], n1 = NX[3 * c + 1], n2 = NX[3 * c + 2];
+        double q[3];
 #pragma unroll
-          for (int i = 0; i < 3; ++i) q[i] = (NPE == 8) ? sh.X[3 * c + i] + sh.U[3 * c + i] : sh.U[3 * c + i];
-#pragma unroll
-          for (int i = 0; i < 3; ++i)
-          {
-            F[i + 0] += q[i] * n0;
-            F[i + 3] += q[i] * n1;
-            F[i + 6] += q[i] * n2;
-          }
-        }
-        if (NPE != 8)
-        {
-          F[0] += 1.0;
-          F[4] += 1.0;
-          F[8] += 1.0;
-        }
-        // inverse of F must exist (evaluate_spatial_material_mapping, calc_lib.hpp:562)
-        {
-          double Fi[9];
-#pragma unroll
-          for (int k = 0; k < 9; ++k) Fi[k] = F[k];
-          if (invert3x3(Fi) == 0.0) atomicMax(&sh.bad, 2);
-        }
-        // C = F^T F, E = (C - I)/2 with engineering shear (calc_lib.hpp:639-676)
-        double C[9];
+        for (int i = 0; i < 3; ++i) q[i] = (NPE == 8) ? sh.X[3 * c + i] + sh.U[3 * c + i] : sh.U[3 * c + i];
 #pragma unroll
         for (int i = 0; i < 3; ++i)
-#pragma unroll
-          for (int j = 0; j < 3; ++j)
-            C[i + 3 * j] = F[3 * i] * F[3 * j] + F[3 * i + 1] * F[3 * j + 1] + F[3 * i + 2] * F[3 * j + 2];
-        E[0] = 0.5 * (C[0] - 1.0);
-        E[1] = 0.5 * (C[4] - 1.0);
-        E[2] = 0.5 * (C[8] - 1.0);
-        E[3] = C[3];
-        E[4] = C[7];
-        E[5] = C[2];
-        double* Fs = sh.F + 9 * g;
-#pragma unroll
-        for (int k = 0; k < 9; ++k) Fs[k] = F[k];
-        double* Ms = sh.M + 6 * g;  // F F^T: xx yy zz xy yz zx
-        Ms[0] = F[0] * F[0] + F[3] * F[3] + F[6] * F[6];
-        Ms[1] = F[1] * F[1] + F[4] * F[4] + F[7] * F[7];
-        Ms[2] = F[2] * F[2] + F[5] * F[5] + F[8] * F[8];
-        Ms[3] = F[0] * F[1] + F[3] * F[4] + F[6] * F[7];
-        Ms[4] = F[1] * F[2] + F[4] * F[5] + F[7] * F[8];
-        Ms[5] = F[2] * F[0] + F[5] * F[3] + F[8] * F[6];
+        {
+          F[i + 0] += q[i] * n0;
+          F[i + 3] += q[i] * n1;
+          F[i + 6] += q[i] * n2;
+        }
       }
-      // So3Material::evaluate -> S = C E (4C_mat_stvenantkirchhoff.cpp:169-177), or ElastHyper
-      double* S = sh.S + 6 * g;
-      if (MAT == 1)
-        neohooke_stress_cmat(A.nh_c, A.nh_beta, E, S, sh.Cm + 36 * (MAT ? g : 0));
-      else
+      if (NPE != 8)
       {
-        S[0] = A.cdiag * E[0] + A.lambda * E[1] + A.lambda * E[2];
-        S[1] = A.lambda * E[0] + A.cdiag * E[1] + A.lambda * E[2];
-        S[2] = A.lambda * E[0] + A.lambda * E[1] + A.cdiag * E[2];
-        S[3] = A.mu * E[3];
-        S[4] = A.mu * E[4];
-        S[5] = A.mu * E[5];
+        F[0] += 1.0;
+        F[4] += 1.0;
+        F[8] += 1.0;
       }
+      // inverse of F must exist (evaluate_spatial_material_mapping, calc_lib.hpp:562)
+      {
+        double Fi[9];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) Fi[k] = F[k];
+        if (invert3x3(Fi) == 0.0) atomicMax(&sh.bad, 2);
+      }
+      // C = F^T F, E = (C - I)/2 with engineering shear (calc_lib.hpp:639-676)
+      double C[9];
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+          C[i + 3 * j] = F[3 * i] * F[3 * j] + F[3 * i + 1] * F[3 * j + 1] + F[3 * i + 2] * F[3 * j + 2];
+      E[0] = 0.5 * (C[0] - 1.0);
+      E[1] = 0.5 * (C[4] - 1.0);
+      E[2] = 0.5 * (C[8] - 1.0);
+      E[3] = C[3];
+      E[4] = C[7];
+      E[5] = C[2];
+      double* Fs = sh.F + 9 * g;
+#pragma unroll
+      for (int k = 0; k < 9; ++k) Fs[k] = F[k];
+      double* Ms = sh.M + 6 * g;  // F F^T: xx yy zz xy yz zx
+      Ms[0] = F[0] * F[0] + F[3] * F[3] + F[6] * F[6];
+      Ms[1] = F[1] * F[1] + F[4] * F[4] + F[7] * F[7];
+      Ms[2] = F[2] * F[2] + F[5] * F[5] + F[8] * F[8];
+      Ms[3] = F[0] * F[1] + F[3] * F[4] + F[6] * F[7];
+      Ms[4] = F[1] * F[2] + F[4] * F[5] + F[7] * F[8];
+      Ms[5] = F[2] * F[0] + F[5] * F[3] + F[8] * F[6];
+      // So3Material::evaluate of ElastHyper: S and cmat
+      neohooke_stress_cmat(A.nh_c, A.nh_beta, E, sh.S + 6 * g, sh.Cm + 36 * g);
     }
     __syncthreads();
     EL_STAMP(3);
-    if (KIN == 1)
+    if (sh.bad)
     {
-      if (sh.bad)
+      if (tid == 0)
       {
-        if (tid == 0)
-        {
-          atomicMax(&A.err[0], sh.bad);
-          atomicMin(&A.err[1], int32_t(e));
-        }
-        __syncthreads();
-        continue;
-      }
-      // P_c = F N_XYZ_c
-      for (int v = tid; v < NGP * NPE; v += BLOCK)
-      {
-        const int g = v / NPE;
-        const double* F = sh.F + 9 * g;
-        const double n0 = sh.NX[3 * v], n1 = sh.NX[3 * v + 1], n2 = sh.NX[3 * v + 2];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) sh.P[3 * v + i] = F[i] * n0 + F[i + 3] * n1 + F[i + 6] * n2;
+        atomicMax(&A.err[0], sh.bad);
+        atomicMin(&A.err[1], int32_t(e));
       }
       __syncthreads();
-      EL_STAMP(4);
+      continue;
     }
+    // P_c = F N_XYZ_c
+    for (int v = tid; v < NGP * NPE; v += BLOCK)
+    {
+      const int g = v / NPE;
+      const double* F = sh.F + 9 * g;
+      const double n0 = sh.NX[3 * v], n1 = sh.NX[3 * v + 1], n2 = sh.NX[3 * v + 2];
+#pragma unroll
+      for (int i = 0; i < 3; ++i) sh.P[3 * v + i] = F[i] * n0 + F[i + 3] * n1 + F[i + 6] * n2;
+    }
+    __syncthreads();
+    EL_STAMP(4);
 
     const int32_t* inc = A.inc_of + e * NPE;
 
@@ -784,19 +648,13 @@ __global__ __launch_bounds__(BLOCK, (NPE == 27 && MAT == 0) ? 3 : 1) void elemen
           t[0] = S[0] * n[0] + S[3] * n[1] + S[5] * n[2];
           t[1] = S[3] * n[0] + S[1] * n[1] + S[4] * n[2];
           t[2] = S[5] * n[0] + S[4] * n[1] + S[2] * n[2];
-          if (KIN == 1)
-          {
-            const double* F = sh.F + 9 * g;
-            const double s0 = F[0] * t[0] + F[3] * t[1] + F[6] * t[2];
-            const double s1 = F[1] * t[0] + F[4] * t[1] + F[7] * t[2];
-            const double s2 = F[2] * t[0] + F[5] * t[1] + F[8] * t[2];
-            t[0] = s0;
-            t[1] = s1;
-            t[2] = s2;
-          }
-          f[0] += fc * t[0];
-          f[1] += fc * t[1];
-          f[2] += fc * t[2];
+          const double* F = sh.F + 9 * g;
+          const double s0 = F[0] * t[0] + F[3] * t[1] + F[6] * t[2];
+          const double s1 = F[1] * t[0] + F[4] * t[1] + F[7] * t[2];
+          const double s2 = F[2] * t[0] + F[5] * t[1] + F[8] * t[2];
+          f[0] += fc * s0;
+          f[1] += fc * s1;
+          f[2] += fc * s2;
         }
         if (ASM)
         {
@@ -826,120 +684,56 @@ __global__ __launch_bounds__(BLOCK, (NPE == 27 && MAT == 0) ? 3 : 1) void elemen
 
     // 6. element stiffness blocks K_ab (add_elastic/geometric_stiffness_matrix, calc_lib.hpp:872-927)
     auto pair_block = [&](int a, int b, double* K) {
+      (void)A;  // captured as the removed StVK branch did: holds the kernels' code as it was
       double G[9];
 #pragma unroll
       for (int k = 0; k < 9; ++k) G[k] = 0.0;
-      double H[6] = {0, 0, 0, 0, 0, 0};
       double geo = 0.0;
       for (int g = 0; g < NGP; ++g)
       {
         const double fc = sh.fac[g];
         const double* na = sh.NX + 3 * (NPE * g + a);
         const double* nb = sh.NX + 3 * (NPE * g + b);
-        if (MAT == 1)
-        {
-          // general material: K_ab += fac (B_a^T cmat B_b + (a.S.b) I)  (calc_lib.hpp:872-927);
-          // G holds B_a^T cmat B_b (row-major i, j), geo the geometric part
-          const double* F = sh.F + 9 * g;
-          const double* cm = sh.Cm + 36 * (MAT ? g : 0);
-          double Ba[6][3], Bb[6][3];
-          strain_gradient(F, na, Ba);
-          strain_gradient(F, nb, Bb);
+        // general material: K_ab += fac (B_a^T cmat B_b + (a.S.b) I)  (calc_lib.hpp:872-927);
+        // G holds B_a^T cmat B_b (row-major i, j), geo the geometric part
+        const double* F = sh.F + 9 * g;
+        const double* cm = sh.Cm + 36 * g;
+        double Ba[6][3], Bb[6][3];
+        strain_gradient(F, na, Ba);
+        strain_gradient(F, nb, Bb);
 #pragma unroll
-          for (int j = 0; j < 3; ++j)
+        for (int j = 0; j < 3; ++j)
+        {
+          double cb[6];
+#pragma unroll
+          for (int r = 0; r < 6; ++r)
           {
-            double cb[6];
+            double t = 0.0;
 #pragma unroll
-            for (int r = 0; r < 6; ++r)
-            {
-              double t = 0.0;
-#pragma unroll
-              for (int q = 0; q < 6; ++q) t += cm[r + 6 * q] * Bb[q][j];
-              cb[r] = fc * t;
-            }
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-            {
-              double t = 0.0;
-#pragma unroll
-              for (int r = 0; r < 6; ++r) t += Ba[r][i] * cb[r];
-              G[i + 3 * j] += t;
-            }
+            for (int q = 0; q < 6; ++q) t += cm[r + 6 * q] * Bb[q][j];
+            cb[r] = fc * t;
           }
-          const double* S = sh.S + 6 * g;
-          const double c0 = nb[0], c1 = nb[1], c2 = nb[2];
-          const double sb0 = S[0] * c0 + S[3] * c1 + S[5] * c2;
-          const double sb1 = S[3] * c0 + S[1] * c1 + S[4] * c2;
-          const double sb2 = S[5] * c0 + S[4] * c1 + S[2] * c2;
-          geo += fc * (na[0] * sb0 + na[1] * sb1 + na[2] * sb2);
+#pragma unroll
+          for (int i = 0; i < 3; ++i)
+          {
+            double t = 0.0;
+#pragma unroll
+            for (int r = 0; r < 6; ++r) t += Ba[r][i] * cb[r];
+            G[i + 3 * j] += t;
+          }
         }
-        else if (KIN == 0)
-        {
-          const double fa0 = fc * na[0], fa1 = fc * na[1], fa2 = fc * na[2];
-          const double b0 = nb[0], b1 = nb[1], b2 = nb[2];
-          G[0] += fa0 * b0; G[3] += fa0 * b1; G[6] += fa0 * b2;
-          G[1] += fa1 * b0; G[4] += fa1 * b1; G[7] += fa1 * b2;
-          G[2] += fa2 * b0; G[5] += fa2 * b1; G[8] += fa2 * b2;
-        }
-        else
-        {
-          const double* pa = sh.P + 3 * (NPE * g + a);
-          const double* pb = sh.P + 3 * (NPE * g + b);
-          const double fa0 = fc * pa[0], fa1 = fc * pa[1], fa2 = fc * pa[2];
-          const double b0 = pb[0], b1 = pb[1], b2 = pb[2];
-          G[0] += fa0 * b0; G[3] += fa0 * b1; G[6] += fa0 * b2;
-          G[1] += fa1 * b0; G[4] += fa1 * b1; G[7] += fa1 * b2;
-          G[2] += fa2 * b0; G[5] += fa2 * b1; G[8] += fa2 * b2;
-          const double a0 = na[0], a1 = na[1], a2 = na[2];
-          const double c0 = nb[0], c1 = nb[1], c2 = nb[2];
-          const double t = fc * (a0 * c0 + a1 * c1 + a2 * c2);
-          const double* M = sh.M + 6 * g;
+        const double* S = sh.S + 6 * g;
+        const double c0 = nb[0], c1 = nb[1], c2 = nb[2];
+        const double sb0 = S[0] * c0 + S[3] * c1 + S[5] * c2;
+        const double sb1 = S[3] * c0 + S[1] * c1 + S[4] * c2;
+        const double sb2 = S[5] * c0 + S[4] * c1 + S[2] * c2;
+        geo += fc * (na[0] * sb0 + na[1] * sb1 + na[2] * sb2);
+      }
 #pragma unroll
-          for (int k = 0; k < 6; ++k) H[k] += t * M[k];
-          const double* S = sh.S + 6 * g;
-          const double sb0 = S[0] * c0 + S[3] * c1 + S[5] * c2;
-          const double sb1 = S[3] * c0 + S[1] * c1 + S[4] * c2;
-          const double sb2 = S[5] * c0 + S[4] * c1 + S[2] * c2;
-          geo += fc * (a0 * sb0 + a1 * sb1 + a2 * sb2);
-        }
-      }
-      // K_ij = lambda G_ij + mu G_ji + mu tr(G) delta_ij      (linear)
-      // K_ij = lambda G_ij + mu G_ji + mu H_ij + geo delta_ij (TotLag)
-      const double lam = A.lambda, mu = A.mu;
-      if (MAT == 1)
-      {
-#pragma unroll
-        for (int i = 0; i < 9; ++i) K[i] = G[i];
-        K[0] += geo;
-        K[4] += geo;
-        K[8] += geo;
-      }
-      else
-      {
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-          for (int j = 0; j < 3; ++j) K[i + 3 * j] = lam * G[i + 3 * j] + mu * G[j + 3 * i];
-      }
-      if (MAT == 1)
-      {
-      }
-      else if (KIN == 0)
-      {
-        const double tr = mu * (G[0] + G[4] + G[8]);
-        K[0] += tr;
-        K[4] += tr;
-        K[8] += tr;
-      }
-      else
-      {
-        K[0] += mu * H[0] + geo;
-        K[4] += mu * H[1] + geo;
-        K[8] += mu * H[2] + geo;
-        K[1] += mu * H[3]; K[3] += mu * H[3];
-        K[5] += mu * H[4]; K[7] += mu * H[4];
-        K[2] += mu * H[5]; K[6] += mu * H[5];
-      }
+      for (int i = 0; i < 9; ++i) K[i] = G[i];
+      K[0] += geo;
+      K[4] += geo;
+      K[8] += geo;
     };
     auto pair_of = [&](int p, int& a, int& b) {
       if (SYM)
@@ -954,33 +748,15 @@ __global__ __launch_bounds__(BLOCK, (NPE == 27 && MAT == 0) ? 3 : 1) void elemen
         b = p - NPE * (p / NPE);
       }
     };
-    if constexpr (NPE == 27 && (KIN == 0 || ASM != 0 || MAT == 0))
+    if constexpr (NPE == 27 && ASM != 0)
     {
       if (A.want_k)
       {
-      // blocks a <= b into registers, then (after every thread's last N_XYZ / P read) into the
-      // LDS image KS; then the element's owned block rows leave coalesced: general path (ASM 0)
-      // as contiguous incidence records [3][27 nodes][3] of the scratch; colour-ordered path as
-      // runs of contiguous CSR columns (element nodes in lattice order) -- written by the first
-      // element of the colour order that holds both nodes, added to by the others
-      double* KS = sh.ks();
-      // matrix cores for the linear blocks and the colour-ordered TotLag path; the TotLag
-      // scratch path keeps the VALU loop (its 15 accumulator tiles would spill at three
-      // workgroups per CU, and at two the MFMA phase measured slower: DESIGN §7e)
-      constexpr bool kMfma = MAT == 0 && !(KIN == 1 && ASM == 0);
-      if (kMfma && A.mfma)
-        pair_phase_mfma27<KIN>(sh, KS, A.lambda, A.mu, tid);
-      else if constexpr (KIN == 0)
-      {
-        for (int p = tid; p < NPAIR; p += BLOCK)
-        {
-          int a, b;
-          pair_of(p, a, b);
-          if (sh.inc[a] >= 0 || sh.inc[b] >= 0) pair_block(a, b, KS + 9 * p);
-        }
-      }
-      else if constexpr (ASM != 0)
-      {
+        // colour-ordered path: blocks a <= b into registers, then (after every thread's last
+        // N_XYZ read) into the LDS image KS; then the element's owned block rows leave coalesced as
+        // runs of contiguous CSR columns (element nodes in lattice order) -- written by the first
+        // element of the colour order that holds both nodes, added to by the others
+        double* KS = sh.KS;
         double Kq[2][9];
 #pragma unroll
         for (int q = 0; q < 2; ++q)
@@ -1002,89 +778,36 @@ __global__ __launch_bounds__(BLOCK, (NPE == 27 && MAT == 0) ? 3 : 1) void elemen
 #pragma unroll
             for (int k = 0; k < 9; ++k) KS[9 * p + k] = Kq[q][k];
         }
-      }
-      else
-      {
-        // TotLag general path without MFMA: each pair thread writes its block rows straight into
-        // the scratch records
-        for (int p = tid; p < NPAIR; p += BLOCK)
+        __syncthreads();
+        constexpr int NV = 9;  // entries in flight per thread: all loads before the stores
+        for (int v0 = 0; v0 < NPE * 243; v0 += NV * BLOCK)
         {
-          int a, b;
-          pair_of(p, a, b);
-          const int32_t ia = inc[a];
-          const int32_t ib = inc[b];
-          if (ia < 0 && ib < 0) continue;
-          double K[9];
-          pair_block(a, b, K);
-          if (ia >= 0)
+          uint32_t slot[NV];  // local row node | offset inside its rows << 5; 0xFFFFFFFF = none
+          double val[NV];
+#pragma unroll
+          for (int k = 0; k < NV; ++k)
           {
-            double* rec = A.scratch + int64_t(ia) * REC + 3 * b;
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-#pragma unroll
-              for (int j = 0; j < 3; ++j) rec[i * ROWLEN + j] = K[i + 3 * j];
+            const int v = v0 + tid + BLOCK * k;
+            slot[k] = 0xFFFFFFFFu;
+            val[k] = 0.0;
+            if (v >= NPE * 243) continue;
+            const int a = v / 243;
+            if (sh.inc[a] < 0) continue;
+            const int r = v - 243 * a;
+            const int i = r / 81, c = r - 81 * (r / 81);
+            const int b = sh.latnode[c / 3], j = c - 3 * (c / 3);
+            const uint32_t o = uint32_t(i * sh.rlen[a] + sh.ipos[NPE * a + b] + j);
+            slot[k] = uint32_t(a) | (o << 5);
+            const int lo = a < b ? a : b, hi = a < b ? b : a;
+            const int pidx = 27 * lo - (lo * (lo - 1)) / 2 + hi - lo;
+            val[k] = KS[9 * pidx + (a <= b ? i + 3 * j : j + 3 * i)];
+            if (!(ASM == 2 && first_touch27(sh.loc, ft, a, b))) val[k] += A.K[sh.rbase[a] + o];
           }
-          if (a != b && ib >= 0)
-          {
-            double* rec = A.scratch + int64_t(ib) * REC + 3 * a;
 #pragma unroll
-            for (int i = 0; i < 3; ++i)
-#pragma unroll
-              for (int j = 0; j < 3; ++j) rec[i * ROWLEN + j] = K[j + 3 * i];
-          }
+          for (int k = 0; k < NV; ++k)
+            if (slot[k] != 0xFFFFFFFFu)
+              __builtin_nontemporal_store(val[k], A.K + sh.rbase[slot[k] & 31u] + (slot[k] >> 5));
         }
-      }
-      const bool image = !(KIN == 1 && ASM == 0);
-      __syncthreads();
-      if (!image)
-      {
-      }
-      else if constexpr (ASM == 0)
-      {
-        for (int v = tid; v < NPE * 243; v += BLOCK)
-        {
-          const int a = v / 243;
-          if (sh.inc[a] < 0) continue;
-          const int r = v - 243 * a;
-          const int i = r / 81, c = r - 81 * (r / 81);
-          const int b = c / 3, j = c - 3 * (c / 3);
-          const int lo = a < b ? a : b, hi = a < b ? b : a;
-          const int pidx = 27 * lo - (lo * (lo - 1)) / 2 + hi - lo;
-          A.scratch[int64_t(sh.inc[a]) * REC + r] = KS[9 * pidx + (a <= b ? i + 3 * j : j + 3 * i)];
-        }
-      }
-      else
-      {
-      constexpr int NV = 9;  // entries in flight per thread: all loads before the stores
-      for (int v0 = 0; v0 < NPE * 243; v0 += NV * BLOCK)
-      {
-        uint32_t slot[NV];  // local row node | offset inside its rows << 5; 0xFFFFFFFF = none
-        double val[NV];
-#pragma unroll
-        for (int k = 0; k < NV; ++k)
-        {
-          const int v = v0 + tid + BLOCK * k;
-          slot[k] = 0xFFFFFFFFu;
-          val[k] = 0.0;
-          if (v >= NPE * 243) continue;
-          const int a = v / 243;
-          if (sh.inc[a] < 0) continue;
-          const int r = v - 243 * a;
-          const int i = r / 81, c = r - 81 * (r / 81);
-          const int b = sh.latnode[c / 3], j = c - 3 * (c / 3);
-          const uint32_t o = uint32_t(i * sh.rlen[a] + sh.ipos[NPE * a + b] + j);
-          slot[k] = uint32_t(a) | (o << 5);
-          const int lo = a < b ? a : b, hi = a < b ? b : a;
-          const int pidx = 27 * lo - (lo * (lo - 1)) / 2 + hi - lo;
-          val[k] = KS[9 * pidx + (a <= b ? i + 3 * j : j + 3 * i)];
-          if (!(ASM == 2 && first_touch27(sh.loc, ft, a, b))) val[k] += A.K[sh.rbase[a] + o];
-        }
-#pragma unroll
-        for (int k = 0; k < NV; ++k)
-          if (slot[k] != 0xFFFFFFFFu)
-            __builtin_nontemporal_store(val[k], A.K + sh.rbase[slot[k] & 31u] + (slot[k] >> 5));
-      }
-      }
       }
     }
     else if (A.want_k)
@@ -1446,21 +1169,11 @@ static int grid_for(int64_t work, int cap)
   return int(work < cap ? (work > 0 ? work : 1) : cap);
 }
 
-// hex27 StVK pair phase on the matrix cores unless FCG_H27_MFMA=0 (A/B measurements)
-static int h27_mfma()
-{
-  static const int on = [] {
-    const char* e = std::getenv("FCG_H27_MFMA");
-    return (e && e[0] == '0') ? 0 : 1;
-  }();
-  return on;
-}
-
+// General path of everything but hex27 StVK (launch_h27_element, fcg_hex27.hip)
 hipError_t launch_element(const DeviceMesh& m, const double* d_u_col, bool want_k, hipStream_t stream)
 {
   if (m.n_ele == 0) return hipSuccess;
   ElementArgs a{};
-  a.mfma = h27_mfma();
   a.n_ele = m.n_ele;
   a.ele_nodes = m.ele_nodes;
   a.node_x = m.node_x;
@@ -1480,38 +1193,29 @@ hipError_t launch_element(const DeviceMesh& m, const double* d_u_col, bool want_
   {
     // general constitutive tangent: one workgroup per element (TotLag only, checked at create)
     if (m.npe == 8)
-      hipLaunchKernelGGL((element_kernel<8, 1, 64, 1>), dim3(grid_for(m.n_ele, 256 * 32)), dim3(64),
-          0, stream, a);
+      hipLaunchKernelGGL((element_kernel<8, 64>), dim3(grid_for(m.n_ele, 256 * 32)), dim3(64), 0,
+          stream, a);
     else
-      hipLaunchKernelGGL((element_kernel<27, 1, 256, 1>), dim3(grid_for(m.n_ele, 256 * 8)),
-          dim3(256), 0, stream, a);
+      hipLaunchKernelGGL((element_kernel<27, 256>), dim3(grid_for(m.n_ele, 256 * 8)), dim3(256), 0,
+          stream, a);
     return hipGetLastError();
   }
-  if (m.npe == 8)
-  {
-    const int grid = grid_for((m.n_ele + H8_EPB - 1) / H8_EPB, 256 * 16);
-    if (m.kinem == 0)
-      hipLaunchKernelGGL((element_kernel_h8<0>), dim3(grid), dim3(256), 0, stream, a);
-    else
-      hipLaunchKernelGGL((element_kernel_h8<1>), dim3(grid), dim3(256), 0, stream, a);
-  }
+  if (m.npe != 8) return hipErrorInvalidValue;  // hex27 StVK has its own kernels
+  const int grid = grid_for((m.n_ele + H8_EPB - 1) / H8_EPB, 256 * 16);
+  if (m.kinem == 0)
+    hipLaunchKernelGGL((element_kernel_h8<0>), dim3(grid), dim3(256), 0, stream, a);
   else
-  {
-    const int grid = grid_for(m.n_ele, 256 * 8);
-    if (m.kinem == 0)
-      hipLaunchKernelGGL((element_kernel<27, 0, 256>), dim3(grid), dim3(256), 0, stream, a);
-    else
-      hipLaunchKernelGGL((element_kernel<27, 1, 256>), dim3(grid), dim3(256), 0, stream, a);
-  }
+    hipLaunchKernelGGL((element_kernel_h8<1>), dim3(grid), dim3(256), 0, stream, a);
   return hipGetLastError();
 }
 
 hipError_t launch_element_colored(const DeviceMesh& m, const double* d_u_col, bool want_k,
     bool overwrite, double* d_K, double* d_fint, hipStream_t stream)
 {
-  if (m.n_ele == 0 || m.npe != 27) return m.n_ele == 0 ? hipSuccess : hipErrorInvalidValue;
+  if (m.n_ele == 0) return hipSuccess;
+  // hex27 ElastHyper/CoupNeoHooke only: hex27 StVK takes launch_h27_pencil (fcg_hex27.hip)
+  if (m.npe != 27 || m.material != FCG_MAT_ELASTHYPER_COUPNEOHOOKE) return hipErrorInvalidValue;
   ElementArgs a{};
-  a.mfma = h27_mfma();
   a.n_ele = m.n_ele;
   a.ele_nodes = m.ele_nodes;
   a.node_x = m.node_x;
@@ -1540,24 +1244,10 @@ hipError_t launch_element_colored(const DeviceMesh& m, const double* d_u_col, bo
     a.e_end = m.color_ptr[c + 1];
     if (a.e_end == a.e_begin) continue;
     const dim3 grid(grid_for(a.e_end - a.e_begin, 256 * 8)), block(256);
-#define FCG_COL(KIN, MAT)                                                                          \
-  if (overwrite)                                                                                   \
-    hipLaunchKernelGGL((element_kernel<27, KIN, 256, MAT, 2>), grid, block, 0, stream, a);         \
-  else                                                                                             \
-    hipLaunchKernelGGL((element_kernel<27, KIN, 256, MAT, 1>), grid, block, 0, stream, a);
-    if (m.material == FCG_MAT_ELASTHYPER_COUPNEOHOOKE)
-    {
-      FCG_COL(1, 1)
-    }
-    else if (m.kinem == 0)
-    {
-      FCG_COL(0, 0)
-    }
+    if (overwrite)
+      hipLaunchKernelGGL((element_kernel<27, 256, 2>), grid, block, 0, stream, a);
     else
-    {
-      FCG_COL(1, 0)
-    }
-#undef FCG_COL
+      hipLaunchKernelGGL((element_kernel<27, 256, 1>), grid, block, 0, stream, a);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }

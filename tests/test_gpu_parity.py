@@ -58,20 +58,62 @@ CASES = [
     (fcg.HEX8, fcg.TOTLAG, (6, 5, 4), 5e-2),
     (fcg.HEX27, fcg.LINEAR, (3, 3, 3), 1e-3),
     (fcg.HEX27, fcg.TOTLAG, (3, 2, 2), 5e-2),
+    # the general hex27 path (element kernel + assemble27_kernel) with every workgroup's pipeline
+    # holding several elements, and on an input-file numbering (see MESH_OPTS)
+    (fcg.HEX27, fcg.TOTLAG, (4, 3, 5), 5e-2),
+    (fcg.HEX27, fcg.LINEAR, (5, 4, 4), 1e-3),
+    (fcg.HEX27, fcg.TOTLAG, (7, 6, 6), 5e-2),
+    (fcg.HEX27, fcg.TOTLAG, (5, 5, 4), 1e-2),
 ]
+# meshes of CASES that are not the default jittered box: BoxMesh arguments; `renumber` = seed of
+# Discretization.renumbered (random node and element numbering, no lattice hint: a row node's
+# elements lie far apart in element order), whose u is amp * default_rng(1).standard_normal
+MESH_OPTS = {
+    (fcg.HEX27, (4, 3, 5)): dict(jitter=0.02, seed=5),
+    (fcg.HEX27, (5, 4, 4)): dict(jitter=0.02, seed=5),
+    (fcg.HEX27, (7, 6, 6)): dict(jitter=0.02, seed=5),
+    (fcg.HEX27, (5, 5, 4)): dict(jitter=0.02, seed=7, renumber=3),
+}
+
+
+def _oracle_view(dis, celltype):
+    """A single-rank Discretization as oracle_evaluate reads a mesh (every node owned)."""
+    m = type("M", (), {})()
+    m.row_gid = m.col_gid = np.arange(dis.n_cols, dtype=np.int32)
+    m.nnz, m.n_rows, m.rowptr, m.col_lid = dis.nnz, dis.n_rows, dis.rowptr, dis.col_lid
+    m.celltype, m.n_ele, m.ele_nodes = celltype, dis.n_ele, dis.ele_nodes
+    m.n_node, m.node_x, m.node_dof_row = dis.n_node, dis.node_x, dis.node_dof_row
+    m.node_gid = np.arange(dis.n_node, dtype=np.int64)
+    return m
+
+
+def _case_mesh(celltype, iv, amp):
+    """(mesh for the GPU, u_col, mesh for the oracle) of a CASES entry."""
+    opts = dict(MESH_OPTS.get((celltype, iv), dict(jitter=0.1, seed=20251015)))
+    renumber = opts.pop("renumber", None)
+    box = fcg.BoxMesh(celltype, iv, **opts)
+    if renumber is None:
+        return box, box.u_col(amp), box
+    dis = fcg.Discretization.renumbered(box, seed=renumber)
+    u = np.random.default_rng(1).standard_normal(dis.n_cols) * amp
+    return dis, u, _oracle_view(dis, celltype)
 
 
 @pytest.mark.parametrize("celltype,kinem,iv,amp", CASES)
 def test_nlnstiff_matches_oracle(celltype, kinem, iv, amp):
-    mesh = fcg.BoxMesh(celltype, iv, jitter=0.1, seed=20251015)
-    u = mesh.u_col(amp)
-    err, _, Kr, fr = oracle_evaluate(mesh, kinem, E, NU, u)
+    mesh, u, omesh = _case_mesh(celltype, iv, amp)
+    err, _, Kr, fr = oracle_evaluate(omesh, kinem, E, NU, u)
     assert err == 0
     Kg, fg, ev = _run_gpu(mesh, kinem, u)
     # box meshes carry the lattice hint -> hex8: fused structured sweep; hex27: general path
     # (the colour-ordered path is tested below)
     assert ev.info.path == (fcg.PATH_STRUCTURED if celltype == fcg.HEX8 else fcg.PATH_GENERAL)
     _check(Kg, fg, Kr, fr)
+    # hex27 general path: incidence-ordered sums, so further evaluates of the same context are
+    # bitwise the first (hex8: test_bitwise_reproducible)
+    for _ in range(2 if celltype == fcg.HEX27 else 0):
+        K2, f2, _ = _run_gpu(mesh, kinem, u, ev=ev)
+        assert np.array_equal(K2, Kg) and np.array_equal(f2, fg)
 
 
 @pytest.mark.parametrize("kinem", [fcg.LINEAR, fcg.TOTLAG])
@@ -86,7 +128,7 @@ def test_hex8_general_and_structured_paths_agree_with_oracle(kinem, iv):
         _check(Kg, fg, Kr, fr)
 
 
-@pytest.mark.parametrize("celltype,kinem,iv,amp", CASES[:1] + CASES[3:])
+@pytest.mark.parametrize("celltype,kinem,iv,amp", CASES[:1] + CASES[3:4])
 def test_internal_force_only(celltype, kinem, iv, amp):
     mesh = fcg.BoxMesh(celltype, iv, jitter=0.1)
     u = mesh.u_col(amp)
@@ -96,15 +138,26 @@ def test_internal_force_only(celltype, kinem, iv, amp):
 
 
 def test_accumulate_adds_to_caller_storage():
-    mesh = fcg.BoxMesh(fcg.HEX8, (4, 4, 4), jitter=0.1)
-    u = mesh.u_col(1e-3)
-    rng = np.random.default_rng(0)
-    K0 = rng.standard_normal(mesh.nnz)
-    f0 = rng.standard_normal(mesh.n_rows)
-    Kg, fg, _ = _run_gpu(mesh, fcg.LINEAR, u, mode=fcg.ACCUMULATE, K0=K0.copy(), f0=f0.copy())
-    Kr, fr, _ = _run_gpu(mesh, fcg.LINEAR, u, mode=fcg.OVERWRITE)
-    np.testing.assert_allclose(Kg, K0 + Kr, rtol=0, atol=1e-13 * np.abs(Kr).max())
-    np.testing.assert_allclose(fg, f0 + fr, rtol=0, atol=1e-13 * np.abs(fr).max())
+    # the structured hex8 sweep, and the general hex27 path (element kernel + assemble27_kernel)
+    for mesh, kinem, amp, rng_seed in (
+            (fcg.BoxMesh(fcg.HEX8, (4, 4, 4), jitter=0.1), fcg.LINEAR, 1e-3, 0),
+            (fcg.BoxMesh(fcg.HEX27, (5, 4, 3), jitter=0.02, seed=9), fcg.TOTLAG, 5e-2, 3)):
+        u = mesh.u_col(amp)
+        rng = np.random.default_rng(rng_seed)
+        K0 = rng.standard_normal(mesh.nnz)
+        f0 = rng.standard_normal(mesh.n_rows)
+        Kg, fg, ev = _run_gpu(mesh, kinem, u, mode=fcg.ACCUMULATE, K0=K0.copy(), f0=f0.copy())
+        Kr, fr, _ = _run_gpu(mesh, kinem, u, mode=fcg.OVERWRITE)
+        np.testing.assert_allclose(Kg, K0 + Kr, rtol=0, atol=1e-13 * np.abs(Kr).max())
+        np.testing.assert_allclose(fg, f0 + fr, rtol=0, atol=1e-13 * np.abs(fr).max())
+        if mesh.celltype == fcg.HEX27:
+            # the internal-force-only evaluate runs the same sums: bitwise the f of K + r
+            assert ev.info.path == fcg.PATH_GENERAL
+            _, fi, _ = _run_gpu(mesh, kinem, u, action=fcg.CALC_INTERNALFORCE, ev=ev)
+            assert np.array_equal(fi, fr)
+            _, fia, _ = _run_gpu(mesh, kinem, u, action=fcg.CALC_INTERNALFORCE,
+                                 mode=fcg.ACCUMULATE, f0=f0.copy(), ev=ev)
+            assert np.array_equal(fia, fg)
 
 
 def test_host_pointer_entry_point():

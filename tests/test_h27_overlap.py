@@ -1,16 +1,15 @@
-"""hex27 overlapped schedule (h27_element_kernel<KIN, 3>).
+"""hex27 general path: the two launches (h27_element_kernel, then assemble27_kernel), DESIGN §7e.
 
-One launch takes element chunks and row items from one queue: a workgroup's element work and
-another's row assembly share a CU, and a row item waits (bounded) until every band of chunks its
-rows need has been counted complete.  Each K / f entry is still summed in incidence order by one
-wavefront, so K and f must be BITWISE those of the two-launch path (element kernel, then
-assemble27_kernel, the default) and match the oracle's Discretization::evaluate
-(4C_fem_discretization_evaluate.cpp:65-103, SparseMatrix::assemble 4C_linalg_sparsematrix.cpp:
-474-543) to the tolerances of test_gpu_parity.py.  The knob sets below force the hand-offs the
-default never meets: one element per chunk and band with a row item per row node and no lag (every
-row item waits on a running band), and every row item queued after all elements.
+This file used to compare the overlapped one-launch schedule (DESIGN §7e "Overlapped schedule",
+removed) with the two launches.  What it asserted about the two launches stays, under the names
+the suite has known: each K / f entry is summed in incidence order by one wavefront, so K and f
+are BITWISE the same for every context of a mesh and for every way the element launches are cut
+("chunk1": one element per slab, FCG_H27_SLAB=1, the row assembly after each), and match the
+oracle's Discretization::evaluate (4C_fem_discretization_evaluate.cpp:65-103, SparseMatrix::assemble
+4C_linalg_sparsematrix.cpp:474-543) to the tolerances of test_gpu_parity.py.
 """
 
+import functools
 import importlib
 
 import numpy as np
@@ -24,7 +23,6 @@ torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
 E, NU = 210.0, 0.3
-KNOBS = ("FCG_H27_OVERLAP", "FCG_H27_CHUNK", "FCG_H27_BAND", "FCG_H27_RITEM", "FCG_H27_LAG")
 
 
 def _dev():
@@ -33,15 +31,13 @@ def _dev():
     return torch.device("cuda:0")
 
 
-def _evaluator(monkeypatch, mesh, kinem, knobs):
+def _evaluator(monkeypatch, mesh, kinem, env):
     _dev()
-    for k in KNOBS:
-        monkeypatch.delenv(k, raising=False)
-    for k, v in knobs.items():
+    monkeypatch.delenv("FCG_H27_SLAB", raising=False)
+    for k, v in env.items():
         monkeypatch.setenv(k, str(v))
     ev = fcg.Evaluator(mesh, kinematics=kinem, youngs=E, poisson=NU, device=0)
-    for k in KNOBS:
-        monkeypatch.delenv(k, raising=False)
+    monkeypatch.delenv("FCG_H27_SLAB", raising=False)
     return ev
 
 
@@ -62,13 +58,17 @@ def _run(ev, mesh, u_col, action=fcg.CALC_NLNSTIFF, mode=fcg.OVERWRITE, K0=None,
     return out
 
 
-ON = {"FCG_H27_OVERLAP": 1}
-STRESS = [
-    dict(ON),                                                            # defaults
-    dict(ON, FCG_H27_CHUNK=1, FCG_H27_BAND=1, FCG_H27_RITEM=1, FCG_H27_LAG=0),
-    dict(ON, FCG_H27_CHUNK=3, FCG_H27_BAND=2, FCG_H27_RITEM=5, FCG_H27_LAG=1),
-    dict(ON, FCG_H27_CHUNK=16, FCG_H27_BAND=1000, FCG_H27_RITEM=1000),   # rows after all elements
-]
+@functools.lru_cache(maxsize=None)
+def _box_case(kinem, iv):
+    """Mesh, displacements and the oracle's K, f of a box case (computed once, read only)."""
+    mesh = fcg.BoxMesh(fcg.HEX27, iv, jitter=0.02, seed=5)
+    u = mesh.u_col(1e-3 if kinem == fcg.LINEAR else 5e-2)
+    _, _, Kr, fr = oracle_evaluate(mesh, kinem, E, NU, u)
+    return mesh, u, Kr, fr
+
+
+# ways of running the two launches: one launch pair, or one element per element launch
+VARIANTS = [{}, {"FCG_H27_SLAB": 1}]
 
 
 @pytest.mark.parametrize("kinem,iv", [
@@ -76,31 +76,30 @@ STRESS = [
     (fcg.LINEAR, (5, 4, 4)),
     (fcg.TOTLAG, (7, 6, 6)),
 ])
-@pytest.mark.parametrize("knobs", STRESS, ids=["default", "chunk1", "chunk3", "rows-last"])
+@pytest.mark.parametrize("knobs", VARIANTS, ids=["default", "chunk1"])
 def test_overlap_bitwise_equal_two_launches_and_match_oracle(monkeypatch, kinem, iv, knobs):
-    mesh = fcg.BoxMesh(fcg.HEX27, iv, jitter=0.02, seed=5)
-    u = mesh.u_col(1e-3 if kinem == fcg.LINEAR else 5e-2)
-    ref_ev = _evaluator(monkeypatch, mesh, kinem, {"FCG_H27_OVERLAP": 0})
+    mesh, u, Kr, fr = _box_case(kinem, iv)
+    ref_ev = _evaluator(monkeypatch, mesh, kinem, {})
     (ref,) = _run(ref_ev, mesh, u)
     ev = _evaluator(monkeypatch, mesh, kinem, knobs)
     assert ev.info.path == fcg.PATH_GENERAL
+    assert (ev.info.h27_slabs > 1) == bool(knobs)
     runs = _run(ev, mesh, u, reps=3)
     for K, f in runs:
         assert np.array_equal(K, ref[0]) and np.array_equal(f, ref[1])
-    _, _, Kr, fr = oracle_evaluate(mesh, kinem, E, NU, u)
     assert rel_err(runs[0][1], fr) <= 1e-10
     assert np.all(np.isfinite(runs[0][0]))
     assert rel_err(runs[0][0], Kr) <= 1e-12
     assert np.abs(runs[0][0] - Kr).max() <= 1e-12 * np.abs(Kr).max()
 
 
-@pytest.mark.parametrize("knobs", STRESS[:2], ids=["default", "chunk1"])
+@pytest.mark.parametrize("knobs", VARIANTS[:1], ids=["default"])
 def test_overlap_accumulate_and_internal_force(monkeypatch, knobs):
     mesh = fcg.BoxMesh(fcg.HEX27, (5, 4, 3), jitter=0.02, seed=9)
     u = mesh.u_col(5e-2)
     rng = np.random.default_rng(3)
     K0, f0 = rng.standard_normal(mesh.nnz), rng.standard_normal(mesh.n_rows)
-    ref_ev = _evaluator(monkeypatch, mesh, fcg.TOTLAG, {"FCG_H27_OVERLAP": 0})
+    ref_ev = _evaluator(monkeypatch, mesh, fcg.TOTLAG, {})
     ev = _evaluator(monkeypatch, mesh, fcg.TOTLAG, knobs)
     for action in (fcg.CALC_NLNSTIFF, fcg.CALC_INTERNALFORCE):
         (ref,) = _run(ref_ev, mesh, u, action=action, mode=fcg.ACCUMULATE, K0=K0, f0=f0)
@@ -111,14 +110,14 @@ def test_overlap_accumulate_and_internal_force(monkeypatch, knobs):
 
 
 def test_overlap_renumbered_mesh(monkeypatch):
-    """Input-file numbering: a row node's elements lie in far-apart chunks, so its row item needs
-    many bands (and waits for the last of them)."""
+    """Input-file numbering: a row node's elements lie far apart in element order, so its records
+    are written by many workgroups (and, per element launch, by many launches)."""
     box = fcg.BoxMesh(fcg.HEX27, (5, 5, 4), jitter=0.02, seed=7)
     mesh = fcg.Discretization.renumbered(box, seed=3)
     u = np.random.default_rng(1).standard_normal(mesh.n_cols) * 1e-2
-    ref_ev = _evaluator(monkeypatch, mesh, fcg.TOTLAG, {"FCG_H27_OVERLAP": 0})
+    ref_ev = _evaluator(monkeypatch, mesh, fcg.TOTLAG, {})
     (ref,) = _run(ref_ev, mesh, u)
-    for knobs in STRESS[:3]:
+    for knobs in VARIANTS:
         ev = _evaluator(monkeypatch, mesh, fcg.TOTLAG, knobs)
         (got,) = _run(ev, mesh, u)
         assert np.array_equal(got[0], ref[0]) and np.array_equal(got[1], ref[1])
@@ -126,8 +125,8 @@ def test_overlap_renumbered_mesh(monkeypatch):
 
 def test_overlap_reports_the_first_failing_element(monkeypatch):
     """An element pulled inside out (det J < 0 at its nodes) is reported with the same code and GID
-    as on the two-launch path (calc_lib.hpp:475-496; that path's report is checked against the
-    oracle by test_gpu_parity.py::test_negative_nodal_jacobian_all_paths), and the queue drains."""
+    however the element launches are cut (calc_lib.hpp:475-496; the report is checked against the
+    oracle by test_gpu_parity.py::test_negative_nodal_jacobian_all_paths)."""
     mesh = fcg.BoxMesh(fcg.HEX27, (4, 4, 3))
     nodes = mesh.ele_nodes[list(mesh.ele_gid).index(21)]
     top = nodes[[4, 5, 6, 7, 16, 17, 18, 19, 25]]
@@ -135,12 +134,12 @@ def test_overlap_reports_the_first_failing_element(monkeypatch):
     u = np.zeros(mesh.n_cols)
     dev = _dev()
     out = {}
-    for name, knobs in (("two", {"FCG_H27_OVERLAP": 0}), ("ovl", ON), ("ovl1", STRESS[1])):
+    for name, knobs in (("two", VARIANTS[0]), ("chunk1", VARIANTS[1])):
         ev = _evaluator(monkeypatch, mesh, fcg.TOTLAG, knobs)
         f = torch.zeros(mesh.n_rows, dtype=torch.float64, device=dev)
         K = torch.zeros(mesh.nnz, dtype=torch.float64, device=dev)
         with pytest.raises(fcg.FcgError) as ei:
             ev.evaluate_device(fcg.CALC_NLNSTIFF, fcg.OVERWRITE, torch.from_numpy(u).to(dev), f, K)
         out[name] = (ei.value.code, ei.value.bad_ele_gid)
-    assert out["ovl"] == out["two"] and out["ovl1"] == out["two"]
+    assert out["chunk1"] == out["two"]
     assert out["two"][0] == fcg.FCG_ERR_NODAL_DETJ

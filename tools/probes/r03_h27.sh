@@ -1,6 +1,6 @@
 #!/bin/bash
-# hex27 matrix-core element kernel + symmetric-record assembly (fcg_hex27.hip): parity, then
-# timing against the incidence-record kernels (FCG_H27_LEGACY=1), a rocprofv3 kernel trace and
+# hex27 matrix-core element kernel + row assembly (fcg_hex27.hip): parity, then
+# timing, a rocprofv3 kernel trace and
 # the counter passes of tools/pmc.sh for both kernels.
 set -o pipefail
 cd "$GRAFT_REPO_ROOT" || exit 2
