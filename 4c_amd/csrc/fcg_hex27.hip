@@ -37,6 +37,8 @@
 //      into the owned CSR rows.
 //  h27_apply_sf_kernel<KIN>  the matrix-free action y = K(u) x, sum-factorised, one wavefront per
 //      workgroup; h27_inc_sum_kernel adds a row node's incidences in incidence order.
+//  h27_diag_kernel<KIN>  the 3 x 3 nodal diagonal blocks of K(u) without a matrix, the action's
+//      structure; h27_diag_rows_kernel sums them per row node, sets the Dirichlet rows, inverts.
 // Fixed summation orders everywhere: bitwise reproducible, no atomics on K or f.
 #include <hip/hip_runtime.h>
 
@@ -1237,6 +1239,412 @@ __global__ __launch_bounds__(256) void h27_inc_sum_kernel(int64_t n_rownodes,
   y[row0 + 2] = y2;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Matrix-free nodal diagonal blocks of K(u) (fcg_tangent_diag): the 3 x 3 block K_aa each element
+// adds at its node a, B_a^T C B_a + K_geo,aa over the Gauss points (calc_lib.hpp:872-927), in
+// closed form for the isotropic StVK C.  With d = dN_a(xi_g), n = J^-T d = grad_X N_a, v = F n:
+//   K_aa = sum_g fac [ (lambda + mu) v v^T + mu |n|^2 F F^T + (n . S n) I ],   S = C E(u)
+// (linear kinematics: F = I and no geometric part).  With M = J^-T (n = M d) the point phase
+// leaves per point A = F M, fac, mu fac M^T M, fac M^T S M and F F^T in LDS, the node phase --
+// lanes (element, node) -- sums the 6 distinct entries over the 27 points with d from the 1-D
+// tables and stores them at the node's incidence; h27_diag_rows_kernel adds a row node's
+// incidences in incidence order.  Gathers, pass order and gradient phase are the action's.
+struct H27DiagArgs {
+  int64_t n_ele;
+  const int32_t* ele_nodes;
+  const double* node_x;
+  const double* u_col;
+  const int32_t* inc_of;
+  const int32_t* ele_dof;  // [n_ele][27] column LID of each element node's first DOF
+  double* de;  // [n_inc + 1][6]: 00 01 02 11 12 22 (the last record: the unowned nodes' stores)
+  int64_t n_inc;
+  double lambda, mu;
+};
+
+template <int KIN>
+__global__ __launch_bounds__(64, 2) void h27_diag_kernel(H27DiagArgs A)
+{
+  constexpr int BT = 64, NE = 2;
+  auto phase_sync = [&]() { __asm__ volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); };
+  constexpr int NSRC = KIN == 0 ? 1 : 2;  // X (linear) or X | u
+  constexpr int kGs = NSRC == 2 ? 18 : 10, kSs = 9;
+  // a point's record, 16-byte aligned pieces: A (9) (lambda + mu) fac | mu fac M^T M (6) | fac M^T S M (6) |
+  // F F^T (6); the two quadratic forms' off-diagonal entries doubled
+  constexpr int PS = KIN == 0 ? 16 : 28;
+  constexpr int oA = 0, oF = 9, oG = 10, oT = 16, oB = 22;
+  auto nv = [](int src, int k, int l) { return 84 * src + 28 * k + l; };  // nodal value
+  __shared__ alignas(16) double pt[NE][27 * PS];   // nodal X | (u) in its first 84 NSRC, then the points' records
+  __shared__ alignas(16) double gr[NE][27 * kGs];  // d(src)_k / dxi_d at point l: l kGs + kSs src + 3 k + d
+  __shared__ double tL[9], tdL[9];
+  __shared__ uint8_t lat[27], posl[27];  // lattice position -> node (= point) number, and back
+  __shared__ int32_t incs[NE][27];        // the pass's incidences of (element, node), -1 = unowned
+  static_assert(84 * NSRC <= 27 * PS, "the nodal values fit the records' LDS");
+  const int tid = threadIdx.x;
+  if (tid < 9)
+  {
+    tL[tid] = c_L1[tid];
+    tdL[tid] = c_dL1[tid];
+  }
+  if (tid < 27)
+  {
+    lat[tid] = c_latnode[tid];
+    const uint32_t pc = c_loc[tid];
+    posl[tid] = uint8_t((pc & 3) + 3 * ((pc >> 2) & 3) + 9 * (pc >> 4));
+  }
+  const double lam = A.lambda, mu = A.mu, cd = lam + 2.0 * mu;
+  constexpr int NIT = NE * 81 * NSRC;
+  constexpr int NLD = (NIT + BT - 1) / BT;
+  // the action's two-stage unconditional gathers (see h27_apply_sf_kernel)
+  double pre[NLD];
+  int32_t ix1[NLD];
+  auto item_ok = [&](int t, int64_t e0) {
+    return t < NIT && e0 >= 0 && e0 + t / (81 * NSRC) < A.n_ele;
+  };
+  auto index_of = [&](int64_t e0, int32_t* ix) {
+#pragma unroll
+    for (int q = 0; q < NLD; ++q)
+    {
+      int t = tid + BT * q;
+      __asm__ volatile("" : "+v"(t));  // index math per pass, not hoisted into live registers
+      const int sl = t / (81 * NSRC), r = t - 81 * NSRC * sl;
+      const int src = r / 81, a = (r - 81 * src) / 3;
+      const int64_t e = item_ok(t, e0) ? e0 + sl : 0;
+      const int32_t* tab = src == 0 ? A.ele_nodes : A.ele_dof;
+      ix[q] = tab[e * 27 + (t < NIT ? a : 0)];
+    }
+  };
+  int32_t incp = 0;  // lane < 27 NE: incidence of (element, node) of the next pass
+  auto value_of = [&](const int32_t* ix, int64_t e0n) {
+    {
+      const int sl = tid / 27;
+      const bool ok = tid < 27 * NE && e0n >= 0 && e0n + sl < A.n_ele;
+      incp = A.inc_of[ok ? (e0n + sl) * 27 + tid - 27 * sl : 0];
+    }
+#pragma unroll
+    for (int q = 0; q < NLD; ++q)
+    {
+      int t = tid + BT * q;
+      __asm__ volatile("" : "+v"(t));
+      const int r = t - 81 * NSRC * (t / (81 * NSRC));
+      const int src = r / 81, d = r - 81 * src - 3 * ((r - 81 * src) / 3);
+      // linear kinematics have no u source (u_col may be null): src is always 0 there
+      const double* base = (NSRC == 1 || src == 0) ? A.node_x : A.u_col;
+      const int32_t at = (src == 0 ? 3 * ix[q] : ix[q]) + d;
+      pre[q] = base[item_ok(t, e0n) ? at : 0];
+    }
+  };
+  // lane roles: gradients (s, line, src), points (s, g), nodes (s, a)
+  const int s27 = tid / 27, r27 = tid - 27 * s27;
+  const double wg = c_w[c_latnode[r27]];  // weight of the lane's point
+  const int sg = tid / (9 * NSRC), rg = tid - 9 * NSRC * sg;
+  // XCD-contiguous passes, as the action
+  const int64_t nch = (A.n_ele + NE - 1) / NE;
+  const int xcd = int(blockIdx.x & 7u);
+  const int64_t per_xcd = (int64_t(gridDim.x) + 7 - xcd) / 8;
+  const int64_t span = (nch + 7) / 8;
+  const int64_t c0 = min(nch, int64_t(xcd) * span), c1 = min(nch, c0 + span);
+  auto first_of = [&](int64_t c) { return c < c1 ? c * NE : int64_t(-1); };
+  int64_t ch = c0 + (blockIdx.x >> 3);
+  index_of(first_of(ch), ix1);
+  value_of(ix1, first_of(ch));
+  index_of(first_of(ch + per_xcd), ix1);
+  for (; ch < c1; ch += per_xcd)
+  {
+    const int64_t e0 = ch * NE;
+    phase_sync();  // the previous pass's node phase has read the records
+#pragma unroll
+    for (int q = 0; q < NLD; ++q)
+    {
+      const int t = tid + BT * q;
+      if (t < NIT)
+      {
+        const int sl = t / (81 * NSRC), r = t - 81 * NSRC * sl;
+        const int src = r / 81, rr = r - 81 * src, a = rr / 3;
+        pt[sl][nv(src, rr - 3 * a, posl[a])] = pre[q];
+      }
+    }
+    if (tid < 27 * NE) incs[tid / 27][tid - 27 * (tid / 27)] = incp;
+    phase_sync();
+    value_of(ix1, first_of(ch + per_xcd));      // next pass: values at last pass's indices
+    index_of(first_of(ch + 2 * per_xcd), ix1);  // pass after next: indices
+    // ---- gradients at the points of line (m1, m2), one source
+    if (sg < NE && e0 + sg < A.n_ele)
+    {
+      const int line = rg / NSRC, src = rg - NSRC * (rg / NSRC);
+      const int m1 = line % 3, m2 = line / 3;
+      double f0[9], f1[9], f2[9];  // L L, L' L, L L' of (i1, i2)
+#pragma unroll
+      for (int i2 = 0; i2 < 3; ++i2)
+#pragma unroll
+        for (int i1 = 0; i1 < 3; ++i1)
+        {
+          const double ly = tL[3 * m1 + i1], dly = tdL[3 * m1 + i1];
+          const double lz = tL[3 * m2 + i2], dlz = tdL[3 * m2 + i2];
+          f0[i1 + 3 * i2] = ly * lz;
+          f1[i1 + 3 * i2] = dly * lz;
+          f2[i1 + 3 * i2] = ly * dlz;
+        }
+      double lx[3][3], dlx[3][3];  // [m0][i0]
+#pragma unroll
+      for (int m0 = 0; m0 < 3; ++m0)
+#pragma unroll
+        for (int i0 = 0; i0 < 3; ++i0)
+        {
+          lx[m0][i0] = tL[3 * m0 + i0];
+          dlx[m0][i0] = tdL[3 * m0 + i0];
+        }
+#pragma unroll 1
+      for (int k = 0; k < 3; ++k)
+      {
+        const double* v = pt[sg] + nv(src, k, 0);
+        double w0[3] = {0.0, 0.0, 0.0}, w1[3] = {0.0, 0.0, 0.0}, w2[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+        for (int j = 0; j < 9; ++j)
+#pragma unroll
+          for (int i0 = 0; i0 < 3; ++i0)
+          {
+            const double x = v[nv(0, 0, i0 + 3 * j)];
+            w0[i0] += f0[j] * x;
+            w1[i0] += f1[j] * x;
+            w2[i0] += f2[j] * x;
+          }
+#pragma unroll
+        for (int m0 = 0; m0 < 3; ++m0)
+        {
+          double* o = gr[sg] + kGs * (m0 + 3 * line) + kSs * src + 3 * k;
+          o[0] = dlx[m0][0] * w0[0] + dlx[m0][1] * w0[1] + dlx[m0][2] * w0[2];
+          o[1] = lx[m0][0] * w1[0] + lx[m0][1] * w1[1] + lx[m0][2] * w1[2];
+          o[2] = lx[m0][0] * w2[0] + lx[m0][1] * w2[1] + lx[m0][2] * w2[2];
+        }
+      }
+    }
+    phase_sync();
+    // ---- point algebra: lanes (s27, g); the nodal values are dead, the gradients are in gr
+    if (s27 < NE && e0 + s27 < A.n_ele)
+    {
+      const int g = r27;  // lattice position of the point
+      const double* G = gr[s27] + kGs * g;
+      double iJ[9];
+#pragma unroll
+      for (int q = 0; q < 9; ++q) iJ[q] = G[q];  // [k][d] row-major = J[d + 3k] col-major
+      const double fac = inv3(iJ) * wg;
+      // n = M d with M[j][d] = iJ[j + 3 d]
+      double* R = pt[s27] + PS * g;
+      double MM[6], MSM[6] = {};
+      double F[3][3] = {}, S[3][3] = {};
+      if constexpr (KIN != 0)
+      {
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+          for (int j = 0; j < 3; ++j)
+            F[i][j] = (i == j ? 1.0 : 0.0) + iJ[j] * G[kSs + 3 * i] + iJ[j + 3] * G[kSs + 3 * i + 1] +
+                      iJ[j + 6] * G[kSs + 3 * i + 2];
+        double C[3][3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+          for (int j = 0; j < 3; ++j) C[i][j] = F[0][i] * F[0][j] + F[1][i] * F[1][j] + F[2][i] * F[2][j];
+        const double ev[6] = {0.5 * (C[0][0] - 1.0), 0.5 * (C[1][1] - 1.0), 0.5 * (C[2][2] - 1.0),
+                              C[0][1], C[1][2], C[0][2]};
+        S[0][0] = cd * ev[0] + lam * (ev[1] + ev[2]);
+        S[1][1] = cd * ev[1] + lam * (ev[0] + ev[2]);
+        S[2][2] = cd * ev[2] + lam * (ev[0] + ev[1]);
+        S[0][1] = S[1][0] = mu * ev[3];
+        S[1][2] = S[2][1] = mu * ev[4];
+        S[0][2] = S[2][0] = mu * ev[5];
+      }
+      int q6 = 0;
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int e = c; e < 3; ++e, ++q6)
+        {
+          MM[q6] = iJ[3 * c] * iJ[3 * e] + iJ[1 + 3 * c] * iJ[1 + 3 * e] + iJ[2 + 3 * c] * iJ[2 + 3 * e];
+          if constexpr (KIN != 0)
+          {
+            double t = 0.0;
+#pragma unroll
+            for (int j = 0; j < 3; ++j)
+              t += iJ[j + 3 * c] * (S[j][0] * iJ[3 * e] + S[j][1] * iJ[1 + 3 * e] + S[j][2] * iJ[2 + 3 * e]);
+            MSM[q6] = t;
+            R[oB + q6] = F[c][0] * F[e][0] + F[c][1] * F[e][1] + F[c][2] * F[e][2];
+          }
+        }
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int d = 0; d < 3; ++d)
+          R[oA + 3 * i + d] = KIN == 0 ? iJ[i + 3 * d]
+                                       : F[i][0] * iJ[3 * d] + F[i][1] * iJ[1 + 3 * d] + F[i][2] * iJ[2 + 3 * d];
+      R[oF] = fac * (lam + mu);
+      const double mf = mu * fac;
+#pragma unroll
+      for (int q = 0; q < 6; ++q)
+      {
+        const double two = (q == 0 || q == 3 || q == 5) ? 1.0 : 2.0;  // off-diagonal: both (d, e) and (e, d)
+        R[oG + q] = two * mf * MM[q];
+        if constexpr (KIN != 0) R[oT + q] = two * fac * MSM[q];
+      }
+    }
+    phase_sync();
+    // ---- nodes: lanes (s27, node at lattice position r27)
+    if (s27 < NE && e0 + s27 < A.n_ele)
+    {
+      const int a0 = r27 % 3, a1 = (r27 / 3) % 3, a2 = r27 / 9;
+      double l0[3], dl0[3], l1[3], dl1[3], l2[3], dl2[3];  // the node's 1-D factors at the 3 points
+#pragma unroll
+      for (int m = 0; m < 3; ++m)
+      {
+        l0[m] = tL[3 * m + a0];
+        dl0[m] = tdL[3 * m + a0];
+        l1[m] = tL[3 * m + a1];
+        dl1[m] = tdL[3 * m + a1];
+        l2[m] = tL[3 * m + a2];
+        dl2[m] = tdL[3 * m + a2];
+      }
+      double k00 = 0.0, k01 = 0.0, k02 = 0.0, k11 = 0.0, k12 = 0.0, k22 = 0.0;
+      const double* P = pt[s27];
+      // fully unrolled: the factors' indices are static, 27 x 28 LDS doubles per lane
+#pragma unroll
+      for (int m2 = 0; m2 < 3; ++m2)
+#pragma unroll
+        for (int m1 = 0; m1 < 3; ++m1)
+        {
+          const double c12 = l1[m1] * l2[m2], c1 = dl1[m1] * l2[m2], c2 = l1[m1] * dl2[m2];
+#pragma unroll
+          for (int m0 = 0; m0 < 3; ++m0)
+          {
+            const double* R = P + PS * (m0 + 3 * m1 + 9 * m2);
+            const double d0 = dl0[m0] * c12, d1 = l0[m0] * c1, d2 = l0[m0] * c2;
+            const double v0 = R[oA] * d0 + R[oA + 1] * d1 + R[oA + 2] * d2;
+            const double v1 = R[oA + 3] * d0 + R[oA + 4] * d1 + R[oA + 5] * d2;
+            const double v2 = R[oA + 6] * d0 + R[oA + 7] * d1 + R[oA + 8] * d2;
+            const double c = R[oF];
+            // d d^T; the records hold the off-diagonal entries of the two quadratic forms doubled
+            const double q00 = d0 * d0, q01 = d0 * d1, q02 = d0 * d2, q11 = d1 * d1, q12 = d1 * d2,
+                         q22 = d2 * d2;
+            // mu fac |n|^2 = d^T (mu fac M^T M) d
+            const double gn = R[oG] * q00 + R[oG + 1] * q01 + R[oG + 2] * q02 + R[oG + 3] * q11 +
+                              R[oG + 4] * q12 + R[oG + 5] * q22;
+            const double w0 = c * v0, w1 = c * v1, w2 = c * v2;
+            if constexpr (KIN == 0)
+            {
+              k00 += w0 * v0 + gn;
+              k01 += w0 * v1;
+              k02 += w0 * v2;
+              k11 += w1 * v1 + gn;
+              k12 += w1 * v2;
+              k22 += w2 * v2 + gn;
+            }
+            else
+            {
+              // fac n . S n = d^T (fac M^T S M) d
+              const double tg = R[oT] * q00 + R[oT + 1] * q01 + R[oT + 2] * q02 + R[oT + 3] * q11 +
+                                R[oT + 4] * q12 + R[oT + 5] * q22;
+              k00 += w0 * v0 + gn * R[oB] + tg;
+              k01 += w0 * v1 + gn * R[oB + 1];
+              k02 += w0 * v2 + gn * R[oB + 2];
+              k11 += w1 * v1 + gn * R[oB + 3] + tg;
+              k12 += w1 * v2 + gn * R[oB + 4];
+              k22 += w2 * v2 + gn * R[oB + 5] + tg;
+            }
+          }
+        }
+      const int32_t k = incs[s27][lat[r27]];
+      // unconditional (an unowned node's values go to the spare record)
+      double* o = A.de + 6 * (k >= 0 ? int64_t(k) : A.n_inc);
+      o[0] = k00;
+      o[1] = k01;
+      o[2] = k02;
+      o[3] = k11;
+      o[4] = k12;
+      o[5] = k22;
+    }
+  }
+}
+
+// dbc[row] = 1 for the Dirichlet rows (a row outside the map raises the solver flag word)
+__global__ __launch_bounds__(256) void h27_diag_mask_kernel(int64_t n_dbc, const int32_t* __restrict__ rows,
+    int64_t n_rows, uint8_t* __restrict__ dbc, int32_t* bad)
+{
+  const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= n_dbc) return;
+  const int32_t row = rows[i];
+  if (row < 0 || row >= n_rows)
+  {
+    atomicMax(bad, 2);
+    return;
+  }
+  dbc[row] = 1;
+}
+
+// Block of each owned row node = the sum of its incidences' 6 values in incidence order,
+// expanded to 3 x 3; a Dirichlet row of the node becomes the unit row, its column stays
+// (SparseMatrix::apply_dirichlet, diagonalblock = true).  diag / dinv: row-major, either may be
+// null; the inverse by block_jacobi_kernel's arithmetic (fcg_solver.hip).
+__global__ __launch_bounds__(256) void h27_diag_rows_kernel(int64_t n_rownodes,
+    const int64_t* __restrict__ inc_ptr, const int32_t* __restrict__ rownode_row0,
+    const double* __restrict__ de, const uint8_t* __restrict__ dbc, double* __restrict__ diag,
+    double* __restrict__ dinv, int32_t* bad)
+{
+  const int64_t r = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (r >= n_rownodes) return;
+  double s[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  const int64_t p0 = inc_ptr[r], p1 = inc_ptr[r + 1];
+  for (int64_t k = p0; k < p1; ++k)
+  {
+#pragma unroll
+    for (int q = 0; q < 6; ++q) s[q] += de[6 * k + q];
+  }
+  double b[3][3] = {{s[0], s[1], s[2]}, {s[1], s[3], s[4]}, {s[2], s[4], s[5]}};
+  if (dbc)
+  {
+    const int32_t row0 = rownode_row0[r];
+#pragma unroll
+    for (int d = 0; d < 3; ++d)
+      if (dbc[row0 + d])
+      {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) b[d][c] = c == d ? 1.0 : 0.0;
+      }
+  }
+  if (diag)
+  {
+#pragma unroll
+    for (int d = 0; d < 3; ++d)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) diag[9 * r + 3 * d + c] = b[d][c];
+  }
+  if (!dinv) return;
+  double m[9];  // column-major, as block_jacobi_kernel
+#pragma unroll
+  for (int d = 0; d < 3; ++d)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) m[d + 3 * c] = b[d][c];
+  const double c00 = m[4] * m[8] - m[7] * m[5], c01 = m[7] * m[2] - m[1] * m[8],
+               c02 = m[1] * m[5] - m[4] * m[2];
+  const double det = m[0] * c00 + m[3] * c01 + m[6] * c02;
+  double* o = dinv + 9 * r;
+  if (det == 0.0 || !(det == det))
+  {
+    atomicMax(bad, 1);
+#pragma unroll
+    for (int q = 0; q < 9; ++q) o[q] = 0.0;
+    return;
+  }
+  const double id = 1.0 / det;
+  o[0] = c00 * id;
+  o[1] = (m[6] * m[5] - m[3] * m[8]) * id;
+  o[2] = (m[3] * m[7] - m[6] * m[4]) * id;
+  o[3] = c01 * id;
+  o[4] = (m[0] * m[8] - m[6] * m[2]) * id;
+  o[5] = (m[6] * m[1] - m[0] * m[7]) * id;
+  o[6] = c02 * id;
+  o[7] = (m[3] * m[2] - m[0] * m[5]) * id;
+  o[8] = (m[0] * m[4] - m[3] * m[1]) * id;
+}
+
 }  // namespace
 
 void upload_h27_tables()
@@ -1418,6 +1826,47 @@ hipError_t launch_h27_apply(const DeviceMesh& m, const double* d_u_col, const do
   const dim3 grid(unsigned((m.n_rownodes + 255) / 256)), block(256);
   hipLaunchKernelGGL(h27_inc_sum_kernel, grid, block, 0, stream, m.n_rownodes, m.inc_ptr,
       m.rownode_row0, m.apply_ye, d_y_row);
+  return hipGetLastError();
+}
+
+hipError_t launch_h27_diag(const DeviceMesh& m, const double* d_u_col, int64_t n_dbc,
+    const int32_t* d_dbc_rows, double* d_diag, double* d_dinv, int32_t* flag, hipStream_t stream)
+{
+  if (m.n_ele > 0)
+  {
+    H27DiagArgs a{};
+    a.n_ele = m.n_ele;
+    a.ele_nodes = m.ele_nodes;
+    a.node_x = m.node_x;
+    a.u_col = d_u_col;
+    a.inc_of = m.inc_of;
+    a.ele_dof = m.apply_dof;
+    a.de = m.diag_de;
+    a.n_inc = m.n_inc;
+    a.lambda = m.lambda;
+    a.mu = m.mu;
+    // persistent, as the action: one wavefront per workgroup, two elements per pass
+    const dim3 grid(unsigned(std::min<int64_t>((m.n_ele + 1) / 2, 256 * 8))), block(64);
+    if (m.kinem == 0)
+      hipLaunchKernelGGL((h27_diag_kernel<0>), grid, block, 0, stream, a);
+    else
+      hipLaunchKernelGGL((h27_diag_kernel<1>), grid, block, 0, stream, a);
+    const hipError_t he = hipGetLastError();
+    if (he != hipSuccess) return he;
+  }
+  if (m.n_rownodes == 0) return hipSuccess;
+  if (n_dbc > 0)
+  {
+    hipError_t he = hipMemsetAsync(m.diag_dbc, 0, size_t(m.n_rows), stream);
+    if (he != hipSuccess) return he;
+    hipLaunchKernelGGL(h27_diag_mask_kernel, dim3(unsigned((n_dbc + 255) / 256)), dim3(256), 0, stream,
+        n_dbc, d_dbc_rows, m.n_rows, m.diag_dbc, flag);
+    he = hipGetLastError();
+    if (he != hipSuccess) return he;
+  }
+  const dim3 grid(unsigned((m.n_rownodes + 255) / 256)), block(256);
+  hipLaunchKernelGGL(h27_diag_rows_kernel, grid, block, 0, stream, m.n_rownodes, m.inc_ptr,
+      m.rownode_row0, m.diag_de, n_dbc > 0 ? m.diag_dbc : nullptr, d_diag, d_dinv, flag);
   return hipGetLastError();
 }
 

@@ -86,6 +86,8 @@ struct DeviceMesh {
   double* gather_dummy = nullptr;   // [4] store target of a row without columns
   double* apply_ye = nullptr;       // [n_inc][3] fcg_tangent_apply's node parts (allocated on first use)
   int32_t* apply_dof = nullptr;     // [n_ele][27] column LID of each element node's first DOF (idem)
+  double* diag_de = nullptr;        // [n_inc + 1][6] fcg_tangent_diag's incidence blocks (allocated on first use)
+  uint8_t* diag_dbc = nullptr;      // [n_rows] fcg_tangent_diag's Dirichlet row marks (idem)
   // hex27 slab schedule (FCG_H27_SLAB): the elements run in slabs of h27_slab consecutive
   // elements; after slab s the row nodes whose last incident element lies in slab s are assembled,
   // so an incidence record lives only from its slab to its row's slab, in a ring of h27_ring
@@ -193,6 +195,12 @@ hipError_t launch_h27_pencil(const DeviceMesh& m, const double* d_u_col, bool wa
 hipError_t launch_h27_apply(const DeviceMesh& m, const double* d_u_col, const double* d_x_col,
     double* d_y_row, hipStream_t stream);
 hipError_t launch_h27_apply_plan(const DeviceMesh& m, hipStream_t stream);  // fills m.apply_dof
+// Matrix-free nodal diagonal blocks of K(u) of hex27 StVK (fcg_tangent_diag): the element kernel
+// writes each owned incidence's 6 values to m.diag_de, a row-node pass sums them, replaces the
+// Dirichlet rows by unit rows and writes the blocks and / or their inverses (9 per row node,
+// row-major).  flag: the solver flag word (1: singular or NaN block, 2: a row outside the map).
+hipError_t launch_h27_diag(const DeviceMesh& m, const double* d_u_col, int64_t n_dbc,
+    const int32_t* d_dbc_rows, double* d_diag, double* d_dinv, int32_t* flag, hipStream_t stream);
 // Node-row gather (FCG_PATH_GATHER, hex8 StVK on any mesh): one wavefront per owned row node
 // (fcg_gather.hip).
 hipError_t gather_precompute(DeviceMesh& m, int64_t n_ele, hipStream_t stream);

@@ -586,6 +586,25 @@ int fcg_spmv_f32(fcg_ctx* ctx, const float* d_K32, const double* d_x_col, double
   return FCG_OK;
 }
 
+// m.apply_dof, the gather plan fcg_tangent_apply and fcg_tangent_diag share (built on first use)
+static int ensure_apply_plan(fcg_ctx* ctx, hipStream_t s, const char* who)
+{
+  fcg::DeviceMesh& m = ctx->mesh;
+  if (m.apply_dof || m.n_ele == 0) return FCG_OK;
+  const size_t bytes = size_t(m.n_ele) * 27 * sizeof(int32_t);
+  hipError_t he = hipMalloc(&m.apply_dof, bytes);
+  if (he == hipSuccess) he = fcg::launch_h27_apply_plan(m, s);
+  if (he != hipSuccess)
+  {
+    if (m.apply_dof) (void)hipFree(m.apply_dof);
+    m.apply_dof = nullptr;
+    ctx->last_error = std::string(who) + ": gather plan: " + hipGetErrorString(he);
+    return fcg_device_error();
+  }
+  ctx->device_bytes += int64_t(bytes);
+  return FCG_OK;
+}
+
 int fcg_tangent_apply(fcg_ctx* ctx, const double* d_u_col, const double* d_x_col, double* d_y_row,
     void* stream)
 {
@@ -611,25 +630,83 @@ int fcg_tangent_apply(fcg_ctx* ctx, const double* d_u_col, const double* d_x_col
     }
     ctx->device_bytes += int64_t(bytes);
   }
-  if (!m.apply_dof && m.n_ele > 0)
-  {
-    const size_t bytes = size_t(m.n_ele) * 27 * sizeof(int32_t);
-    hipError_t he = hipMalloc(&m.apply_dof, bytes);
-    if (he == hipSuccess) he = fcg::launch_h27_apply_plan(m, s);
-    if (he != hipSuccess)
-    {
-      if (m.apply_dof) (void)hipFree(m.apply_dof);
-      m.apply_dof = nullptr;
-      ctx->last_error = std::string("fcg_tangent_apply: gather plan: ") + hipGetErrorString(he);
-      return fcg_device_error();
-    }
-    ctx->device_bytes += int64_t(bytes);
-  }
+  if (const int rc = ensure_apply_plan(ctx, s, "fcg_tangent_apply")) return rc;
   const hipError_t he = fcg::launch_h27_apply(m, d_u_col, d_x_col, d_y_row, s);
   if (he != hipSuccess)
   {
     ctx->last_error = std::string("HIP: ") + hipGetErrorString(he);
     return fcg_device_error();
+  }
+  return FCG_OK;
+}
+
+int fcg_tangent_diag(fcg_ctx* ctx, const double* d_u_col, int64_t n_dbc, const int32_t* d_dbc_rows,
+    double* d_diag, double* d_dinv, void* stream)
+{
+  if (!ctx) return FCG_ERR_ARG;
+  fcg::DeviceMesh& m = ctx->mesh;
+  if (m.npe != 27 || m.material != FCG_MAT_STVK || !m.inc_of || !m.inc_ptr || !m.rownode_row0)
+  {
+    ctx->last_error = "fcg_tangent_diag: hex27 St.Venant-Kirchhoff contexts only";
+    return FCG_ERR_ARG;
+  }
+  if (3 * m.n_rownodes != m.n_rows)
+  {
+    ctx->last_error = "fcg_tangent_diag: every owned row must belong to an owned node's DOF triple";
+    return FCG_ERR_ARG;
+  }
+  if (!d_diag && !d_dinv)
+  {
+    ctx->last_error = "fcg_tangent_diag: neither d_diag nor d_dinv given";
+    return FCG_ERR_ARG;
+  }
+  if (n_dbc < 0 || (n_dbc > 0 && !d_dbc_rows) || (m.n_rows > 0 && m.kinem != 0 && !d_u_col))
+  {
+    ctx->last_error = "fcg_tangent_diag: missing u or Dirichlet rows";
+    return FCG_ERR_ARG;
+  }
+  (void)hipSetDevice(ctx->device);
+  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+  if (!m.diag_de)
+  {
+    const size_t bytes = size_t(m.n_inc + 1) * 6 * sizeof(double);  // + the spare record
+    const size_t mbytes = size_t(std::max<int64_t>(m.n_rows, 1));
+    hipError_t he = hipMalloc(&m.diag_de, bytes);
+    if (he == hipSuccess) he = hipMalloc(&m.diag_dbc, mbytes);
+    if (he != hipSuccess)
+    {
+      if (m.diag_de) (void)hipFree(m.diag_de);
+      m.diag_de = nullptr;
+      m.diag_dbc = nullptr;
+      ctx->last_error = std::string("fcg_tangent_diag: hipMalloc: ") + hipGetErrorString(he);
+      return fcg_device_error();
+    }
+    ctx->device_bytes += int64_t(bytes + mbytes);
+  }
+  if (const int rc = ensure_apply_plan(ctx, s, "fcg_tangent_diag")) return rc;
+  int32_t bad = 0;
+  int32_t* flag = m.err + 2;  // the solver flag word: evaluate's sticky flags are left alone
+  hipError_t he = hipMemsetAsync(flag, 0, sizeof(int32_t), s);
+  if (he == hipSuccess) he = fcg::launch_h27_diag(m, d_u_col, n_dbc, d_dbc_rows, d_diag, d_dinv, flag, s);
+  if (he == hipSuccess && d_dinv)
+  {
+    he = hipMemcpyAsync(&bad, flag, sizeof(bad), hipMemcpyDeviceToHost, s);
+    if (he == hipSuccess) he = hipStreamSynchronize(s);
+  }
+  if (he != hipSuccess)
+  {
+    ctx->last_error = std::string("HIP: ") + hipGetErrorString(he);
+    return fcg_device_error();
+  }
+  if (bad == 2)
+  {
+    ctx->last_error = "fcg_tangent_diag: a Dirichlet row outside the row map";
+    return FCG_ERR_ARG;
+  }
+  if (bad)
+  {
+    ctx->last_error = "singular diagonal node block (fcg_tangent_diag)";
+    return FCG_ERR_SINGULAR;
   }
   return FCG_OK;
 }

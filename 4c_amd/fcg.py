@@ -133,7 +133,7 @@ EXPORTS = ["fcg_create", "fcg_destroy", "fcg_last_error", "fcg_evaluate", "fcg_e
            "fcg_device_alloc", "fcg_device_free", "fcg_memcpy_h2d", "fcg_memcpy_d2h",
            "fcg_memset_device", "fcg_set_timing", "fcg_get_timing", "fcg_get_info",
            "fcg_get_diagnostics", "fcg_get_create_phases", "fcg_measure_peaks", "fcg_measure_hbm", "fcg_spmv", "fcg_dirichlet_apply",
-           "fcg_pcg_solve", "fcg_spmv_f32", "fcg_tangent_apply", "fcg_box_stencil_apply", "fcg_box_transfer", "fcg_block_jacobi_setup", "fcg_block_jacobi_apply", "fcg_chebyshev_step", "fcg_node_transfer",
+           "fcg_pcg_solve", "fcg_spmv_f32", "fcg_tangent_apply", "fcg_tangent_diag", "fcg_box_stencil_apply", "fcg_box_transfer", "fcg_block_jacobi_setup", "fcg_block_jacobi_apply", "fcg_chebyshev_step", "fcg_node_transfer",
            "fcg_neumann_surface", "fcg_neumann_volume",
            "fcg_graph_build_device", "fcg_get_graph",
            "fcg_tsi_create", "fcg_tsi_destroy", "fcg_tsi_last_error", "fcg_tsi_evaluate_device",
@@ -206,6 +206,7 @@ def lib():
                                 ctypes.POINTER(ctypes.c_int), _dp, vp]
     L.fcg_spmv_f32.argtypes = [vp, vp, vp, vp, vp]
     L.fcg_tangent_apply.argtypes = [vp, vp, vp, vp, vp]
+    L.fcg_tangent_diag.argtypes = [vp, vp, ctypes.c_int64, vp, vp, vp, vp]
     L.fcg_box_stencil_apply.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, vp]
     L.fcg_box_transfer.argtypes = [ctypes.c_int] * 8 + [vp, vp, vp, vp, vp, ctypes.c_int, vp]
     L.fcg_block_jacobi_setup.argtypes = [vp, vp, vp, vp]
@@ -756,6 +757,20 @@ class Evaluator:
         may be None for linear kinematics."""
         rc = lib().fcg_tangent_apply(self._h, _tensor_ptr(u_col), _tensor_ptr(x_col),
                                      _tensor_ptr(y_row), self._stream(stream))
+        if rc != 0:
+            self._raise(rc, -1)
+
+    def tangent_diag(self, u_col, dbc_rows=None, diag=None, dinv=None, stream=None):
+        """The 3 x 3 nodal diagonal blocks of K(u) without a matrix (fcg_tangent_diag; hex27 StVK):
+        `diag` receives the blocks, `dinv` their inverses, 9 doubles per owned node, row-major, in
+        the order of fcg_block_jacobi_setup's blocks; either may be None, not both.  dbc_rows
+        (int32 device tensor): rows replaced by unit rows, as dirichlet_apply does to K.  u_col
+        may be None for linear kinematics.  With dinv the call waits for the stream and raises for
+        a singular block; with diag only it is asynchronous."""
+        n_dbc = 0 if dbc_rows is None else int(dbc_rows.numel())
+        rc = lib().fcg_tangent_diag(self._h, _tensor_ptr(u_col), n_dbc,
+                                    _tensor_ptr(dbc_rows) if n_dbc else None, _tensor_ptr(diag),
+                                    _tensor_ptr(dinv), self._stream(stream))
         if rc != 0:
             self._raise(rc, -1)
 

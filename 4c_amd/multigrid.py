@@ -319,11 +319,19 @@ class _Level(_LevelOps):
         self.mf_u = None
         self.stencil = None  # rediscretised box levels: fcg_box_stencil_apply instead of K
         self.mf_dbc = torch.as_tensor(np.asarray(dbc_rows, dtype=np.int64), device=device)
+        self.mf_dbc32 = torch.as_tensor(self.rows, device=device)  # fcg_tangent_diag's row list
 
     def stream(self):
         return torch.cuda.current_stream(self.dev)
 
     def setup_diag(self):
+        if self.K is None:
+            # no assembled tangent: the blocks of K(u) at the state set_state gave, formed element
+            # by element (fcg_tangent_diag), the Dirichlet rows as unit rows
+            if self.mf_u is None and self.ev.kinematics != fcg.LINEAR:
+                raise RuntimeError("matrix-free diagonal: set_state(u) before the solve")
+            self.ev.tangent_diag(self.mf_u, self.mf_dbc32, dinv=self.dinv, stream=self.stream())
+            return
         rc = fcg.lib().fcg_block_jacobi_setup(self.ev._h, _ptr(self.K), _ptr(self.dinv),
                                               ctypes.c_void_p(self.stream().cuda_stream))
         if rc != 0:
@@ -484,6 +492,9 @@ class CycleFCG:
         negative), re-estimates the fine level's lambda_max and restarts once; a second failure
         raises MultigridError."""
         f0 = self.levels[0]
+        if K is None and getattr(self, "needs_matrix", True):
+            raise ValueError("solve(None, ...): this solver reads the assembled K (Multigrid needs "
+                             "matrix_free=True and outer_matrix_free=True to run without it)")
         self._prepare(K)
         why, last = None, (None, None)
         for attempt in range(2 if self.retry_lmax else 1):
@@ -575,7 +586,7 @@ class CycleFCG:
         x.zero_()
         if bn == 0.0:
             return 0, 0.0
-        key = (b.data_ptr(), x.data_ptr(), b.numel(), f0.K.data_ptr(),
+        key = (b.data_ptr(), x.data_ptr(), b.numel(), None if f0.K is None else f0.K.data_ptr(),
                None if f0.mf_u is None else f0.mf_u.data_ptr(),
                tuple(l.lmax for l in self.levels))
         g = getattr(self, "_graph", None)
@@ -790,6 +801,9 @@ class Multigrid(CycleFCG):
             self._vcycle(0, b, x)
             if self.outer_matrix_free:
                 self._outer(f0, b, x)
+            if not self.needs_matrix:  # the matrix-free diagonal's kernels
+                f0.ev.tangent_diag(f0.mf_u, f0.mf_dbc32, dinv=f0.dinv, stream=f0.stream())
+                f0.dinv.zero_()
             sc = torch.zeros((), **f64)
             torch.dot(b, x, out=sc)
             torch.div(sc, sc + 1.0, out=sc)
@@ -811,7 +825,14 @@ class Multigrid(CycleFCG):
         if self.levels[0].matrix_free:
             out[0]["operator"] = "matrix-free (fcg_tangent_apply)"
             out[0]["outer_operator"] = "matrix-free" if self.outer_matrix_free else "assembled K"
+        out[0]["diag"] = "matrix-free" if getattr(self, "_diag_matrix_free", False) else "assembled K"
         return out
+
+    @property
+    def needs_matrix(self):
+        """False when no part of a solve reads the assembled K: solve(None, b, x, ...) is allowed
+        and takes the fine level's block-Jacobi blocks from fcg_tangent_diag at set_state's u."""
+        return not (self.levels[0].matrix_free and self.outer_matrix_free)
 
     def set_state(self, u_col):
         """The displacement the next solve's tangent was evaluated at (the matrix-free fine
@@ -824,6 +845,7 @@ class Multigrid(CycleFCG):
         t0 = time.perf_counter()
         f0 = self.levels[0]
         f0.K = K
+        self._diag_matrix_free = K is None
         if self.mixed:
             if f0.K32 is None or f0.K32.numel() != K.numel():
                 f0.K32 = torch.empty(K.numel(), dtype=torch.float32, device=K.device)

@@ -99,13 +99,17 @@ def accept_linear_solve(solve, tol, it, rescue, rec):
 class StaticNewton:
     def __init__(self, evaluator, fext_row, dbc_rows, tol_res=1e-10, tol_inc=1e-10, max_iter=20,
                  lin_rtol=1e-13, lin_max_iter=100000, forcing=None, linear_solver=None,
-                 rescue_bad_newton_solve=True):
+                 rescue_bad_newton_solve=True, assemble_tangent=True):
         """forcing: ForcingTerm (None: Constant at lin_rtol).  linear_solver: an object with
         solve(K, b, x, rtol, max_iter) -> (iterations, relative residual), e.g.
         multigrid.Multigrid (None: the library's block-Jacobi PCG).
         rescue_bad_newton_solve: NOX's "Rescue Bad Newton Solve" (4C default true,
         4C_inpar_solver_nonlin.cpp:65-69): a linear solve that stops above its tolerance still
-        gives the step (recorded in history, with a warning); false: raise."""
+        gives the step (recorded in history, with a warning); false: raise.
+        assemble_tangent=False: no K is allocated or assembled -- each step evaluates the internal
+        force only and hands the linear solver K = None, which needs a solver whose `needs_matrix`
+        is False (multigrid.Multigrid(matrix_free=True, outer_matrix_free=True): operator and
+        block-Jacobi blocks element by element at the step's u)."""
         info = evaluator.info
         self.ev = evaluator
         self.dev = torch.device("cuda", evaluator.device)
@@ -116,7 +120,11 @@ class StaticNewton:
         f64 = dict(dtype=torch.float64, device=self.dev)
         self.fext = torch.as_tensor(np.asarray(fext_row, dtype=np.float64)).to(self.dev)
         self.dbc = torch.as_tensor(np.asarray(dbc_rows, dtype=np.int32)).to(self.dev)
-        self.K = torch.empty(self.nnz, **f64)
+        self.assemble_tangent = bool(assemble_tangent)
+        if not self.assemble_tangent and getattr(linear_solver, "needs_matrix", True) is not False:
+            raise ValueError("assemble_tangent=False needs a linear_solver whose needs_matrix is "
+                             "False (one that never reads K); the library's PCG reads it")
+        self.K = torch.empty(self.nnz, **f64) if self.assemble_tangent else None
         self.fint = torch.empty(self.n, **f64)
         self.r = torch.empty(self.n, **f64)
         self.du = torch.empty(self.n, **f64)
@@ -155,7 +163,8 @@ class StaticNewton:
         ndu = float("inf")
         nr_old = lin_abs = None
         for it in range(self.max_iter + 1):
-            self.ev.evaluate_device(fcg.CALC_NLNSTIFF, fcg.OVERWRITE, u, self.fint, self.K)
+            self.ev.evaluate_device(fcg.CALC_NLNSTIFF if self.assemble_tangent else fcg.CALC_INTERNALFORCE,
+                                    fcg.OVERWRITE, u, self.fint, self.K)
             torch.sub(self.fint, self.fext, out=self.r)
             self.ev.dirichlet_apply(self.dbc, self.K, self.r, self.freact)
             nr = float(torch.linalg.vector_norm(self.r))

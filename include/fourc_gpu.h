@@ -263,6 +263,25 @@ int fcg_pcg_solve(fcg_ctx* ctx, const double* d_K_vals, const double* d_b_row, d
 int fcg_block_jacobi_setup(fcg_ctx* ctx, const double* d_K_vals, double* d_dinv, void* stream);
 int fcg_block_jacobi_apply(fcg_ctx* ctx, const double* d_dinv, const double* d_r_row, double* d_z_row,
     double scale, int accumulate, void* stream);
+/* The 3 x 3 nodal diagonal blocks of K(u) without a matrix: what fcg_block_jacobi_setup picks out
+ * of the assembled tangent, formed element by element.  Per element, node a and Gauss point, with
+ * n = grad_X N_a and v = F n (F = I for linear kinematics),
+ *   K_aa = sum_g fac [ (lambda + mu) v v^T + mu |n|^2 F F^T + (n . S n) I ],  S = C E(u)
+ * (B_a^T C B_a + K_geo,aa of 4C_solid_3D_ele_calc_lib.hpp:872-927 for the isotropic StVK C), summed
+ * per owned row node in incidence order -- deterministic, equal to the assembled K's blocks to
+ * rounding.  The n_dbc rows d_dbc_rows (device, row LIDs) are replaced by unit rows, their columns
+ * stay (fcg_dirichlet_apply on K); n_dbc = 0: the blocks of K(u) before Dirichlet rows.  d_diag:
+ * the blocks, d_dinv: their inverses (fcg_block_jacobi_setup's arithmetic), 9 doubles per owned
+ * node, row-major, block k of the context's k-th row node as fcg_block_jacobi_setup's d_dinv;
+ * either may be NULL, not both.  hex27 St.Venant-Kirchhoff contexts whose owned rows are all owned
+ * nodes' DOF triples (else FCG_ERR_ARG); u_col may be NULL for linear kinematics.  With d_dinv the
+ * call returns after `stream` drained, FCG_ERR_SINGULAR for a singular or non-finite block and
+ * FCG_ERR_ARG for a Dirichlet row outside the row map (the solver flag word, never evaluate's
+ * sticky flags); with d_diag only it is asynchronous like fcg_tangent_apply and such a row is
+ * skipped.  Uses per-context buffers (6 doubles per owned incidence and a byte per row, allocated
+ * on the first call, counted in device_bytes): calls on one context must not run concurrently. */
+int fcg_tangent_diag(fcg_ctx* ctx, const double* d_u_col, int64_t n_dbc, const int32_t* d_dbc_rows,
+    double* d_diag, double* d_dinv, void* stream);
 /* One Chebyshev smoothing step with the block-Jacobi preconditioner, fused per node (the update of
  * the multigrid smoother, 4c_amd/multigrid.py CycleFCG._cheb): with r = b - y (y = A x, computed
  * by the caller) and z = D^-1 r,

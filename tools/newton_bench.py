@@ -45,6 +45,9 @@ ap.add_argument("--mg-matrix-free", action="store_true",
 ap.add_argument("--mg-outer-matrix-free", action="store_true",
                 help="with --mg-matrix-free: the outer flexible CG applies the same tangent "
                      "element by element too (the assembled K still sets the smoother's blocks)")
+ap.add_argument("--no-assembled-tangent", action="store_true",
+                help="with --mg --mg-matrix-free --mg-outer-matrix-free: K is never assembled; the "
+                     "smoother's nodal blocks come from fcg_tangent_diag at each step's u")
 ap.add_argument("--mg-coarse", default="auto", choices=["auto", "dense", "pcg", "amg"],
                 help="coarsest-level solver of the geometric multigrid")
 ap.add_argument("--amg", action="store_true",
@@ -54,6 +57,8 @@ ap.add_argument("--amg-native", action="store_true",
 ap.add_argument("--renumber", action="store_true",
                 help="solve on the box renumbered as an input-file mesh (no lattice, random order)")
 a = ap.parse_args()
+if a.no_assembled_tangent and not (a.mg and a.mg_matrix_free and a.mg_outer_matrix_free):
+    ap.error("--no-assembled-tangent requires --mg --mg-matrix-free --mg-outer-matrix-free")
 ct = fcg.HEX8 if a.celltype == "hex8" else fcg.HEX27
 kin = fcg.LINEAR if a.kinem == "linear" else fcg.TOTLAG
 t0 = time.perf_counter()
@@ -93,7 +98,8 @@ class Timed(newton.StaticNewton):
         for it in range(self.max_iter + 1):
             torch.cuda.synchronize()
             t_a = time.perf_counter()
-            self.ev.evaluate_device(fcg.CALC_NLNSTIFF, fcg.OVERWRITE, u, self.fint, self.K)
+            self.ev.evaluate_device(fcg.CALC_NLNSTIFF if self.assemble_tangent else fcg.CALC_INTERNALFORCE,
+                                    fcg.OVERWRITE, u, self.fint, self.K)
             torch.cuda.synchronize()
             t_b = time.perf_counter()
             torch.sub(self.fint, self.fext, out=self.r)
@@ -125,6 +131,9 @@ class Timed(newton.StaticNewton):
             t_d = time.perf_counter()
             ndu = float(torch.linalg.vector_norm(self.du))
             u += self.du
+            if diag_ms:
+                rec["diag_setup_ms"] = diag_ms.pop()
+                diag_ms.clear()
             rec.update(solve_ms=1e3 * (t_d - t_c), pcg_iter=li, pcg_relres=lr, eta=eta, norm_inc=ndu)
             self.history.append(rec)
             print(json.dumps(rec), file=sys.stderr, flush=True)
@@ -134,6 +143,7 @@ class Timed(newton.StaticNewton):
 
 
 mg = None
+diag_ms = []
 if a.mg:
     t_mg = time.perf_counter()
     mg = importlib.import_module("4c_amd.multigrid").Multigrid(
@@ -146,6 +156,18 @@ if a.mg:
     print(f"multigrid setup {time.perf_counter() - t_mg:.1f} s: {json.dumps(mg.describe())}",
           file=sys.stderr, flush=True)
     t_setup = time.perf_counter() - t0
+    # the fine level's block-Jacobi setup of each solve (fcg_block_jacobi_setup on the assembled K,
+    # or fcg_tangent_diag), synchronised wall clock; a restarted solve keeps its last
+    _setup_diag = mg.levels[0].setup_diag
+
+    def _timed_setup_diag():
+        torch.cuda.synchronize()
+        t_s = time.perf_counter()
+        _setup_diag()
+        torch.cuda.synchronize()
+        diag_ms.append(1e3 * (time.perf_counter() - t_s))
+
+    mg.levels[0].setup_diag = _timed_setup_diag
 if a.amg or a.amg_native:
     t_mg = time.perf_counter()
     amg_mod = importlib.import_module("4c_amd.amg")
@@ -159,7 +181,8 @@ if a.amg or a.amg_native:
     t_setup = time.perf_counter() - t0
 nt = Timed(ev, fext, dbc, lin_max_iter=a.lin_max_iter, tol_res=a.tol * max(np.linalg.norm(fext), 1e-300), tol_inc=a.tol,
            lin_rtol=a.lin_rtol, max_iter=40,
-           forcing=newton.ForcingTerm(a.forcing, constant=a.lin_rtol), linear_solver=mg)
+           forcing=newton.ForcingTerm(a.forcing, constant=a.lin_rtol), linear_solver=mg,
+           assemble_tangent=not a.no_assembled_tangent)
 # the kernels of the Newton step launched once on scratch data (setup: HIP loads a kernel's code
 # object at its first launch, ~0.3 s of config 3's first Newton step otherwise)
 t_w = time.perf_counter()
@@ -175,13 +198,18 @@ torch.cuda.synchronize()
 t_newton = time.perf_counter() - t1
 h = nt.history
 # the tangent at the solution (before Dirichlet rows) is symmetric for StVK: x.(K y) == y.(K x)
-ev.evaluate_device(fcg.CALC_NLNSTIFF, fcg.OVERWRITE, u, nt.fint, nt.K)
+ev.evaluate_device(fcg.CALC_INTERNALFORCE if a.no_assembled_tangent else fcg.CALC_NLNSTIFF,
+                   fcg.OVERWRITE, u, nt.fint, nt.K)
 gen = torch.Generator(device="cpu").manual_seed(7)
 xv = torch.randn(mesh.n_rows, generator=gen, dtype=torch.float64).to(u.device)
 yv = torch.randn(mesh.n_rows, generator=gen, dtype=torch.float64).to(u.device)
 Kx, Ky = torch.empty_like(xv), torch.empty_like(yv)
-ev.spmv(nt.K, xv, Kx)
-ev.spmv(nt.K, yv, Ky)
+if a.no_assembled_tangent:  # the same check on the matrix-free action
+    ev.tangent_apply(u, xv, Kx)
+    ev.tangent_apply(u, yv, Ky)
+else:
+    ev.spmv(nt.K, xv, Kx)
+    ev.spmv(nt.K, yv, Ky)
 sym = abs(float(torch.dot(xv, Ky)) - float(torch.dot(yv, Kx))) / float(
     torch.linalg.vector_norm(xv) * torch.linalg.vector_norm(Ky))
 r_final = float(torch.linalg.vector_norm(nt.fint - nt.fext)) / max(np.linalg.norm(fext), 1e-300)
@@ -197,6 +225,19 @@ if a.mg and a.mg_matrix_free:
     e1.record()
     torch.cuda.synchronize()
     apply_ms = e0.elapsed_time(e1) / 20
+# the matrix-free diagonal pass (fcg_tangent_diag, blocks only: asynchronous) at the solution,
+# hipEvents over 10 back-to-back calls
+diag_pass_ms = None
+if a.mg and a.mg_matrix_free and a.celltype == "hex27":
+    blocks = torch.empty(3 * mesh.n_rows, dtype=torch.float64, device=u.device)
+    ev.tangent_diag(u, nt.dbc, diag=blocks)
+    e0.record()
+    for _ in range(10):
+        ev.tangent_diag(u, nt.dbc, diag=blocks)
+    e1.record()
+    torch.cuda.synchronize()
+    diag_pass_ms = e0.elapsed_time(e1) / 10
+    del blocks
 del xv, yv, Kx, Ky
 out = {"config": f"{a.celltype}-{a.kinem}-{a.n}^3-cantilever", "forcing": a.forcing,
        "converged": True, "tangent_symmetry_rel": sym,
@@ -207,6 +248,9 @@ out = {"config": f"{a.celltype}-{a.kinem}-{a.n}^3-cantilever", "forcing": a.forc
                          f"SA-AMG-FCG (Chebyshev {a.mg_nu})" if a.amg else
                          f"SA-AMG-FCG native C ABI (Chebyshev {a.mg_nu})" if a.amg_native else
                          "block-Jacobi PCG"),
+       "assembled_tangent": not a.no_assembled_tangent,
+       "diag_setup_ms": [r.get("diag_setup_ms") for r in h[:-1]], "tangent_diag_ms": diag_pass_ms,
+       "outside_solve_ms": [r["assembly_ms"] + r["dbc_ms"] for r in h],
        "mesh": "renumbered (input-file order, no lattice)" if a.renumber else "GridGenerator box",
        "mg_levels": mg.describe() if mg else None, "elements": mesh.n_ele,
        "dofs": mesh.n_rows, "nnz": mesh.nnz, "h27_slabs": int(ev.info.h27_slabs),
