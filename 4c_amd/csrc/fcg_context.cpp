@@ -861,7 +861,7 @@ void build_h27_ring(int64_t n_ele, int64_t S, int lag, const std::vector<int64_t
 
 void free_mesh(fcg::DeviceMesh& m)
 {
-  void* ptrs[] = {m.apply_ye, m.apply_dof, m.diag_de, m.diag_dbc, m.gather_dummy, m.multi_ptr, m.rec_row0, m.rec_meta, m.rec_base, m.rec_ele, m.rec_a, m.rec_tmap, m.ele_orig, m.inc_ele, m.inc_a, m.asm_order, m.ele_x,
+  void* ptrs[] = {m.ele_mat, m.apply_ye, m.apply_dof, m.diag_de, m.diag_dbc, m.gather_dummy, m.multi_ptr, m.rec_row0, m.rec_meta, m.rec_base, m.rec_ele, m.rec_a, m.rec_tmap, m.ele_orig, m.inc_ele, m.inc_a, m.asm_order, m.ele_x,
       m.ele_dof, m.ele_nodes, m.ele_gid, m.node_x, m.node_dof_col, m.inc_of, m.inc_ptr,
       m.rownode_row0, m.inc_pos, m.rowptr, m.scratch, m.err, m.elem_at, m.lat_x, m.lat_dof,
       m.plane_rec,
@@ -2014,6 +2014,99 @@ int fcg_get_info(const fcg_ctx* ctx, fcg_info* info)
   info->path = m.path;
   info->h27_slabs =
       m.path == FCG_PATH_GENERAL && m.h27s ? int32_t(std::max<int64_t>(1, m.h27_nslab)) : 0;
+  return FCG_OK;
+}
+
+int fcg_set_element_materials(fcg_ctx* ctx, int32_t n_mat, const double* youngs,
+    const double* poisson, const int32_t* ele_mat)
+{
+  if (!ctx) return FCG_ERR_ARG;
+  fcg::DeviceMesh& m = ctx->mesh;
+  auto refuse = [&](const std::string& why) {
+    ctx->last_error = "fcg_set_element_materials: " + why;
+    return FCG_ERR_ARG;
+  };
+  // every check comes before the first change: a refused call leaves the context as it was
+  if (n_mat < 0) return refuse("n_mat = " + std::to_string(n_mat) + " must be >= 0");
+  if (n_mat > 0)
+  {
+    if (m.path == FCG_PATH_STRUCTURED || m.path == FCG_PATH_COLORED)
+      return refuse(std::string("the ") + (m.path == FCG_PATH_STRUCTURED ? "structured sweep" : "coloured lattice assembly") +
+                    " takes one material per context; create the context with FCG_PATH_GATHER (hex8 "
+                    "St.Venant-Kirchhoff) or FCG_PATH_GENERAL");
+    if (!youngs || !poisson || (m.n_ele > 0 && !ele_mat))
+      return refuse("n_mat > 0 needs youngs, poisson and ele_mat (one of them is NULL)");
+    // Mat::PAR::StVenantKirchhoff parameter checks, as fcg_create's
+    for (int32_t k = 0; k < n_mat; ++k)
+    {
+      if (!(youngs[k] > 0.0))
+        return refuse("youngs[" + std::to_string(k) + "] = " + std::to_string(youngs[k]) + " must be > 0");
+      if (!(poisson[k] < 0.5) || !(poisson[k] >= -1.0))
+        return refuse("poisson[" + std::to_string(k) + "] = " + std::to_string(poisson[k]) +
+                      " must lie in [-1;0.5)");
+    }
+    for (int64_t e = 0; e < m.n_ele; ++e)
+      if (ele_mat[e] < 0 || ele_mat[e] >= n_mat)
+        return refuse("ele_mat[" + std::to_string(e) + "] = " + std::to_string(ele_mat[e]) +
+                      " outside [0, n_mat = " + std::to_string(n_mat) + ")");
+  }
+  (void)hipSetDevice(ctx->device);
+  // queued evaluates read the table that is about to go
+  hipError_t he = hipStreamSynchronize(ctx->stream);
+  if (he == hipSuccess && ctx->pending && ctx->pending_stream != ctx->stream)
+    he = hipStreamSynchronize(ctx->pending_stream);
+  const int64_t tab_bytes = m.n_ele * 4 * int64_t(sizeof(double));
+  double* fresh = nullptr;
+  if (he == hipSuccess && n_mat > 0 && m.n_ele > 0)
+  {
+    // the constants of fcg_create, by the same host arithmetic
+    std::vector<double> c(size_t(n_mat) * 4, 0.0);
+    for (int32_t k = 0; k < n_mat; ++k)
+    {
+      const double nu = poisson[k];
+      if (m.material == FCG_MAT_STVK)
+      {
+        const double mfac = youngs[k] / ((1.0 + nu) * (1.0 - 2.0 * nu));
+        c[4 * k + 0] = mfac * nu;
+        c[4 * k + 1] = mfac * 0.5 * (1.0 - 2.0 * nu);
+        c[4 * k + 2] = mfac * (1.0 - nu);
+      }
+      else
+      {
+        c[4 * k + 0] = youngs[k] / (4.0 * (1.0 + nu));
+        c[4 * k + 1] = nu / (1.0 - 2.0 * nu);
+      }
+    }
+    // FCG_PATH_GATHER keeps its elements in storage-slot (Morton) order
+    std::vector<int32_t> orig;
+    if (m.path == FCG_PATH_GATHER)
+    {
+      orig.resize(m.n_ele);
+      he = hipMemcpy(orig.data(), m.ele_orig, sizeof(int32_t) * size_t(m.n_ele), hipMemcpyDeviceToHost);
+    }
+    std::vector<double> tab(size_t(m.n_ele) * 4);
+    for (int64_t i = 0; i < m.n_ele; ++i)
+    {
+      const int64_t e = orig.empty() ? i : orig[i];
+      for (int q = 0; q < 4; ++q) tab[4 * i + q] = c[4 * size_t(ele_mat[e]) + q];
+    }
+    int64_t unused = 0;
+    if (he == hipSuccess) he = upload(&fresh, tab.data(), m.n_ele * 4, unused);
+  }
+  if (he != hipSuccess)
+  {
+    if (fresh) (void)hipFree(fresh);
+    ctx->last_error = std::string("fcg_set_element_materials: HIP: ") + hipGetErrorString(he);
+    return fcg_device_error();
+  }
+  if (m.ele_mat)
+  {
+    (void)hipFree(m.ele_mat);
+    ctx->device_bytes -= tab_bytes;
+  }
+  m.ele_mat = fresh;
+  if (fresh) ctx->device_bytes += tab_bytes;
+  m.n_mat = n_mat;
   return FCG_OK;
 }
 

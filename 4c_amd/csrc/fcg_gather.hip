@@ -116,6 +116,7 @@ struct GatherArgs {
   int32_t* err;
   double* dummy;             // [3] target of the stores of a row without columns
   StVK mat;
+  const double* ele_mat;     // [n_ele][4] TAB: lambda, mu, cdiag, 0 of each storage slot's element
 };
 
 // hex8 corner n in 4C order: parametric coordinate signs
@@ -178,7 +179,10 @@ __device__ inline double wave_sum(double v)
   return ((r[0] + r[1]) + r[2]) + r[3];
 }
 
-template <int KIN, bool WANT_K, bool OVERWRITE, bool MULTI>
+// TAB: per-element material constants (A.ele_mat) instead of the uniform A.mat -- a lane works on
+// its slot's element throughout, so it carries that element's constants: the stress of stage 2 and
+// the block combination of stage 3 then hold per slot, before the row sum of stage 4
+template <int KIN, bool WANT_K, bool OVERWRITE, bool MULTI, bool TAB = false>
 __global__ __launch_bounds__(64, 2) void gather_h8_kernel(GatherArgs A)
 {
   using Sh = GatherShared<KIN, MULTI>;
@@ -253,6 +257,18 @@ __global__ __launch_bounds__(64, 2) void gather_h8_kernel(GatherArgs A)
       gv[2 * k + 1] = v.y;
     }
   };
+  // TAB: the constants of slot j's element, with the Gauss-point factors one record ahead
+  auto load_m = [&](const RecRegs& r, double* mv) {
+    if constexpr (TAB)
+    {
+      const int64_t el = max(r.ele, 0);
+      const double2* p = reinterpret_cast<const double2*>(A.ele_mat + el * 4);
+      const double2 v = p[0], w = p[1];
+      mv[0] = v.x;
+      mv[1] = v.y;
+      mv[2] = w.x;
+    }
+  };
   auto load_u = [&](int32_t dof, double* u) {
     u[0] = A.u_col[dof];
     u[1] = A.u_col[dof + 1];
@@ -277,6 +293,8 @@ __global__ __launch_bounds__(64, 2) void gather_h8_kernel(GatherArgs A)
   load_x(nx1, xn1, dof1);
   load_u(dofc, uc);
   load_g(cur, gc);
+  double mc[3] = {0.0, 0.0, 0.0};
+  load_m(cur, mc);
   double fA0 = 0.0, fA1 = 0.0, fA2 = 0.0;
   int bad_code = 0, bad_ele = 0x7FFFFFFF;
   // the prologue's loads have landed before the loop: the loop header then carries only the
@@ -297,6 +315,8 @@ __global__ __launch_bounds__(64, 2) void gather_h8_kernel(GatherArgs A)
     load_x(nx2, xn2, dof2);
     load_u(dof1, u1);
     load_g(nx1, g1);
+    double m1[3] = {0.0, 0.0, 0.0};
+    load_m(nx1, m1);
 
     const bool first = (cur.meta >> 4) & 1, last = (cur.meta >> 5) & 1;
     const int64_t base = cur.base;
@@ -417,7 +437,8 @@ __global__ __launch_bounds__(64, 2) void gather_h8_kernel(GatherArgs A)
         const double C7 = F[3] * F[6] + F[4] * F[7] + F[5] * F[8];
         const double C2 = F[6] * F[0] + F[7] * F[1] + F[8] * F[2];
         const double E0 = 0.5 * (C0 - 1.0), E1 = 0.5 * (C4 - 1.0), E2 = 0.5 * (C8 - 1.0);
-        const StVK& m = A.mat;
+        StVK m = A.mat;
+        if constexpr (TAB) m = StVK{mc[0], mc[1], mc[2]};
         const double S0 = m.cdiag * E0 + m.lambda * E1 + m.lambda * E2;
         const double S1 = m.lambda * E0 + m.cdiag * E1 + m.lambda * E2;
         const double S2 = m.lambda * E0 + m.lambda * E1 + m.cdiag * E2;
@@ -509,7 +530,7 @@ __global__ __launch_bounds__(64, 2) void gather_h8_kernel(GatherArgs A)
         }
       }
       // G[3 r + c] = sum_g fac (.)_r (.)_c -> K_ab[r + 3 c] = lambda G_rc + mu G_cr (+ I terms)
-      const double lam = A.mat.lambda, mu = A.mat.mu;
+      const double lam = TAB ? mc[0] : A.mat.lambda, mu = TAB ? mc[1] : A.mat.mu;
 #pragma unroll
       for (int rr = 0; rr < 3; ++rr)
 #pragma unroll
@@ -682,6 +703,9 @@ __global__ __launch_bounds__(64, 2) void gather_h8_kernel(GatherArgs A)
     }
 #pragma unroll
     for (int k = 0; k < 10; ++k) gc[k] = g1[k];
+    if constexpr (TAB)
+#pragma unroll
+      for (int k = 0; k < 3; ++k) mc[k] = m1[k];
     dofc = dof1;
     dof1 = dof2;
   }
@@ -821,6 +845,7 @@ hipError_t launch_gather_h8(const DeviceMesh& m, const double* d_u_col, bool wan
   a.err = m.err;
   a.dummy = m.gather_dummy;
   a.mat = StVK{m.lambda, m.mu, m.cdiag};
+  a.ele_mat = m.ele_mat;
   // one-wave workgroups, as many as the LDS keeps resident on every CU, a multiple of the 8 XCDs,
   // each a contiguous block of records / nodes
   // workgroups per CU: two waves per SIMD.  (Linear kinematics would fit nine by LDS and registers
@@ -833,28 +858,42 @@ hipError_t launch_gather_h8(const DeviceMesh& m, const double* d_u_col, bool wan
   auto grid_of = [&](int64_t work) {
     return dim3{static_cast<unsigned>(std::max<int64_t>(8, std::min<int64_t>(want, (work + 7) / 8 * 8))), 1, 1};
   };
-#define FCG_GATHER(KIN, MULTI, WORK)                                                               \
-  if ((WORK) > 0)                                                                                  \
-  {                                                                                                \
-    const dim3 grid = grid_of(WORK);                                                               \
-    if (want_k && overwrite)                                                                       \
-      hipLaunchKernelGGL((gather_h8_kernel<KIN, true, true, MULTI>), grid, block, 0, stream, a);   \
-    else if (want_k)                                                                               \
-      hipLaunchKernelGGL((gather_h8_kernel<KIN, true, false, MULTI>), grid, block, 0, stream, a);  \
-    else if (overwrite)                                                                            \
-      hipLaunchKernelGGL((gather_h8_kernel<KIN, false, true, MULTI>), grid, block, 0, stream, a);  \
-    else                                                                                           \
-      hipLaunchKernelGGL((gather_h8_kernel<KIN, false, false, MULTI>), grid, block, 0, stream, a); \
+#define FCG_GATHER(KIN, MULTI, WORK, TAB)                                                               \
+  if ((WORK) > 0)                                                                                       \
+  {                                                                                                     \
+    const dim3 grid = grid_of(WORK);                                                                    \
+    if (want_k && overwrite)                                                                            \
+      hipLaunchKernelGGL((gather_h8_kernel<KIN, true, true, MULTI, TAB>), grid, block, 0, stream, a);   \
+    else if (want_k)                                                                                    \
+      hipLaunchKernelGGL((gather_h8_kernel<KIN, true, false, MULTI, TAB>), grid, block, 0, stream, a);  \
+    else if (overwrite)                                                                                 \
+      hipLaunchKernelGGL((gather_h8_kernel<KIN, false, true, MULTI, TAB>), grid, block, 0, stream, a);  \
+    else                                                                                                \
+      hipLaunchKernelGGL((gather_h8_kernel<KIN, false, false, MULTI, TAB>), grid, block, 0, stream, a); \
   }
-  if (m.kinem == 0)
+  // a context with a material table (fcg_set_element_materials) takes the TAB instantiations
+  if (m.ele_mat)
   {
-    FCG_GATHER(0, false, m.n_rec_single)
-    FCG_GATHER(0, true, m.n_multi)
+    if (m.kinem == 0)
+    {
+      FCG_GATHER(0, false, m.n_rec_single, true)
+      FCG_GATHER(0, true, m.n_multi, true)
+    }
+    else
+    {
+      FCG_GATHER(1, false, m.n_rec_single, true)
+      FCG_GATHER(1, true, m.n_multi, true)
+    }
+  }
+  else if (m.kinem == 0)
+  {
+    FCG_GATHER(0, false, m.n_rec_single, false)
+    FCG_GATHER(0, true, m.n_multi, false)
   }
   else
   {
-    FCG_GATHER(1, false, m.n_rec_single)
-    FCG_GATHER(1, true, m.n_multi)
+    FCG_GATHER(1, false, m.n_rec_single, false)
+    FCG_GATHER(1, true, m.n_multi, false)
   }
 #undef FCG_GATHER
   return hipGetLastError();

@@ -184,6 +184,9 @@ struct H27Args {
   const int64_t* rowptr;
   double* K;
   double* fint;
+  // TAB instantiations (fcg_set_element_materials): [n_ele][4] lambda, mu, cdiag, 0 of each column
+  // element instead of the uniform constants above
+  const double* ele_mat;
 };
 
 typedef double f64x4_t __attribute__((ext_vector_type(4)));
@@ -231,7 +234,10 @@ __device__ inline bool first_holder(int cls, uint32_t nb)
 
 // ASM: 0 = records for the row assembly; 1 = pencil order, add into K; 2 = pencil order, the first
 // holder writes (OVERWRITE)
-template <int KIN, int ASM>
+// TAB: per-element material constants.  Two elements are in flight: the producer wave forms ep's
+// Gauss-point factors (the stress: ep's constants) while the consumers combine ec's blocks (ec's
+// constants), so each side reads the record of its own element -- a uniform (scalar) load.
+template <int KIN, int ASM, bool TAB = false>
 __global__ __launch_bounds__(kBlk, 2) void h27_element_kernel(H27Args A)
 {
   constexpr bool PEN = ASM != 0;
@@ -255,7 +261,7 @@ __global__ __launch_bounds__(kBlk, 2) void h27_element_kernel(H27Args A)
     sh.loc[tid] = c_loc[tid];
     sh.latnode[tid] = c_latnode[tid];
   }
-  const double lam = A.lambda, mu = A.mu;
+  const double lam_u = A.lambda, mu_u = A.mu;
 
   // the elements of this workgroup, in sequence: e = blockIdx.x + k gridDim.x, or (pencil order)
   // the pencils pen_begin + blockIdx.x + k gridDim.x, each walked in x order.  Every thread walks
@@ -582,12 +588,30 @@ __global__ __launch_bounds__(kBlk, 2) void h27_element_kernel(H27Args A)
           }
           // S = C E (fill_cmat, 4C_mat_stvenantkirchhoff.cpp:115-145)
           double S[3][3];
-          S[0][0] = A.cdiag * E[0] + A.lambda * (E[1] + E[2]);
-          S[1][1] = A.cdiag * E[1] + A.lambda * (E[0] + E[2]);
-          S[2][2] = A.cdiag * E[2] + A.lambda * (E[0] + E[1]);
-          S[0][1] = S[1][0] = A.mu * E[3];
-          S[1][2] = S[2][1] = A.mu * E[4];
-          S[0][2] = S[2][0] = A.mu * E[5];
+          if constexpr (TAB)
+          {
+            // the constants of ep, the element this wave produces (the consumers hold ec's)
+            const double* pm = A.ele_mat + 4 * ep;
+            const double p_lam = pm[0], p_mu = pm[1], p_cd = pm[2];
+            // the contraction the uniform kernels compile to, spelt out: a table whose entries equal
+            // the context's own material then gives their bits
+            S[0][0] = fma(p_cd, E[0], p_lam * (E[1] + E[2]));
+            S[1][1] = fma(p_cd, E[1], p_lam * (E[0] + E[2]));
+            S[2][2] = fma(p_cd, E[2], p_lam * (E[0] + E[1]));
+            S[0][1] = S[1][0] = p_mu * E[3];
+            S[1][2] = S[2][1] = p_mu * E[4];
+            S[0][2] = S[2][0] = p_mu * E[5];
+          }
+          else
+          {
+            // (kept word for word: the uniform kernels' instruction streams depend on it)
+            S[0][0] = A.cdiag * E[0] + A.lambda * (E[1] + E[2]);
+            S[1][1] = A.cdiag * E[1] + A.lambda * (E[0] + E[2]);
+            S[2][2] = A.cdiag * E[2] + A.lambda * (E[0] + E[1]);
+            S[0][1] = S[1][0] = A.mu * E[3];
+            S[1][2] = S[2][1] = A.mu * E[4];
+            S[0][2] = S[2][0] = A.mu * E[5];
+          }
           // T = F J^-1, R = fac F S J^-1
           double FS[3][3];
 #pragma unroll
@@ -644,6 +668,12 @@ __global__ __launch_bounds__(kBlk, 2) void h27_element_kernel(H27Args A)
       const int a_c = va ? a_l : 0, b_c = vb ? b_l : 0;
       const f64x4_t zero4 = {0.0, 0.0, 0.0, 0.0};
       const int b = 16 * bt + r16;
+      double lam = lam_u, mu = mu_u;
+      if constexpr (TAB)
+      {
+        lam = A.ele_mat[4 * ec];
+        mu = A.ele_mat[4 * ec + 1];
+      }
 
       // 3. TotLag: mu H + geo I.  Per Gauss point one MFMA over k (K = 3, padded to 4) gives
       //    c_ab = d_a^T W d_b, and H += c_ab M_g on the lanes; a second MFMA with the same B operand
@@ -883,6 +913,7 @@ struct H27ApplyArgs {
   double* ye;  // [n_inc + 1][3] (the last triple: target of the unowned nodes' stores)
   int64_t n_inc;
   double lambda, mu, cdiag;
+  const double* ele_mat;  // TAB: [n_ele][4] lambda, mu, cdiag, 0 of each column element
 };
 
 // The action sum-factorised over the tensor-product structure of hex27.  With L_p(x_m), L'_p(x_m)
@@ -895,7 +926,9 @@ struct H27ApplyArgs {
 //   nodes      lanes (element, node line (a1, a2), component i): Q contracted over (m1, m2) with
 //              the line's factors, then over m0 for the line's three nodes -- 99 FMA instead of 729.
 // Four phases per pass (Q reuses the nodal values' LDS).
-template <int KIN>
+// TAB: per-element material constants -- a wavefront holds two elements, the point phase's lane
+// (s27, g) takes those of its element e0 + s27.
+template <int KIN, bool TAB = false>
 __global__ __launch_bounds__(64, 2) void h27_apply_sf_kernel(H27ApplyArgs A)
 {
   // one wavefront per workgroup holds NE = 2 whole elements (54 of 64 lanes) and its phases are
@@ -932,7 +965,7 @@ __global__ __launch_bounds__(64, 2) void h27_apply_sf_kernel(H27ApplyArgs A)
     posl[tid] = uint8_t((pc & 3) + 3 * ((pc >> 2) & 3) + 9 * (pc >> 4));
     wl[tid] = c_w[c_latnode[tid]];
   }
-  const double lam = A.lambda, mu = A.mu, cd = A.cdiag;
+  const double lam_u = A.lambda, mu_u = A.mu, cd_u = A.cdiag;
   constexpr int NLD = (NE * 81 * NSRC + BT - 1) / BT;
   // the gathers in two stages, one pass apart, so that no wait on a dependent load falls inside a
   // pass: stage 1 reads the element's node / DOF index of each item for the pass after next
@@ -1014,6 +1047,16 @@ __global__ __launch_bounds__(64, 2) void h27_apply_sf_kernel(H27ApplyArgs A)
     }
     if (tid < 27 * NE) incs[tid / 27][tid - 27 * (tid / 27)] = incp;
     phase_sync();
+    // TAB: the constants of the lane's element of this pass, issued before the next passes' gathers
+    // (the point phase's wait then does not cover those) and landing behind the gradient phase
+    double lam = lam_u, mu = mu_u, cd = cd_u;
+    if constexpr (TAB)
+    {
+      const double* pm = A.ele_mat + 4 * (s27 < NE && e0 + s27 < A.n_ele ? e0 + s27 : e0);
+      lam = pm[0];
+      mu = pm[1];
+      cd = pm[2];
+    }
     e0pre = first_of(ch + per_xcd);
     value_of(ix1, e0pre);                        // next pass: values at last pass's indices
     index_of(first_of(ch + 2 * per_xcd), ix1);  // pass after next: indices
@@ -1259,9 +1302,11 @@ struct H27DiagArgs {
   double* de;  // [n_inc + 1][6]: 00 01 02 11 12 22 (the last record: the unowned nodes' stores)
   int64_t n_inc;
   double lambda, mu;
+  const double* ele_mat;  // TAB: [n_ele][4] lambda, mu, cdiag, 0 of each column element
 };
 
-template <int KIN>
+// TAB: per-element material constants, per lane as in h27_apply_sf_kernel.
+template <int KIN, bool TAB = false>
 __global__ __launch_bounds__(64, 2) void h27_diag_kernel(H27DiagArgs A)
 {
   constexpr int BT = 64, NE = 2;
@@ -1291,7 +1336,7 @@ __global__ __launch_bounds__(64, 2) void h27_diag_kernel(H27DiagArgs A)
     const uint32_t pc = c_loc[tid];
     posl[tid] = uint8_t((pc & 3) + 3 * ((pc >> 2) & 3) + 9 * (pc >> 4));
   }
-  const double lam = A.lambda, mu = A.mu, cd = lam + 2.0 * mu;
+  const double lam_u = A.lambda, mu_u = A.mu, cd_u = lam_u + 2.0 * mu_u;
   constexpr int NIT = NE * 81 * NSRC;
   constexpr int NLD = (NIT + BT - 1) / BT;
   // the action's two-stage unconditional gathers (see h27_apply_sf_kernel)
@@ -1365,6 +1410,14 @@ __global__ __launch_bounds__(64, 2) void h27_diag_kernel(H27DiagArgs A)
     }
     if (tid < 27 * NE) incs[tid / 27][tid - 27 * (tid / 27)] = incp;
     phase_sync();
+    double lam = lam_u, mu = mu_u, cd = cd_u;
+    if constexpr (TAB)
+    {
+      const double* pm = A.ele_mat + 4 * (s27 < NE && e0 + s27 < A.n_ele ? e0 + s27 : e0);
+      lam = pm[0];
+      mu = pm[1];
+      cd = lam + 2.0 * mu;
+    }
     value_of(ix1, first_of(ch + per_xcd));      // next pass: values at last pass's indices
     index_of(first_of(ch + 2 * per_xcd), ix1);  // pass after next: indices
     // ---- gradients at the points of line (m1, m2), one source
@@ -1718,7 +1771,16 @@ hipError_t launch_h27_element(const DeviceMesh& m, const double* d_u_col, bool w
   // so that every workgroup keeps several elements in its two-element pipeline
   const int64_t cap = m.h27_nslab > 1 ? m.h27_el_grid : 256 * 8;
   const dim3 grid(unsigned(n < cap ? n : cap)), block(kBlk);
-  if (m.kinem == 0)
+  a.ele_mat = m.ele_mat;
+  // a context with a material table (fcg_set_element_materials) takes the TAB instantiations
+  if (m.ele_mat)
+  {
+    if (m.kinem == 0)
+      hipLaunchKernelGGL((h27_element_kernel<0, 0, true>), grid, block, 0, stream, a);
+    else
+      hipLaunchKernelGGL((h27_element_kernel<1, 0, true>), grid, block, 0, stream, a);
+  }
+  else if (m.kinem == 0)
     hipLaunchKernelGGL((h27_element_kernel<0, 0>), grid, block, 0, stream, a);
   else
     hipLaunchKernelGGL((h27_element_kernel<1, 0>), grid, block, 0, stream, a);
@@ -1815,7 +1877,15 @@ hipError_t launch_h27_apply(const DeviceMesh& m, const double* d_u_col, const do
       return e ? std::max<int64_t>(8, std::atoll(e)) : int64_t(256 * 8);
     }();
     const dim3 grid(unsigned(std::min<int64_t>((m.n_ele + 1) / 2, cap))), block(64);
-    if (m.kinem == 0)
+    a.ele_mat = m.ele_mat;
+    if (m.ele_mat)
+    {
+      if (m.kinem == 0)
+        hipLaunchKernelGGL((h27_apply_sf_kernel<0, true>), grid, block, 0, stream, a);
+      else
+        hipLaunchKernelGGL((h27_apply_sf_kernel<1, true>), grid, block, 0, stream, a);
+    }
+    else if (m.kinem == 0)
       hipLaunchKernelGGL((h27_apply_sf_kernel<0>), grid, block, 0, stream, a);
     else
       hipLaunchKernelGGL((h27_apply_sf_kernel<1>), grid, block, 0, stream, a);
@@ -1847,7 +1917,15 @@ hipError_t launch_h27_diag(const DeviceMesh& m, const double* d_u_col, int64_t n
     a.mu = m.mu;
     // persistent, as the action: one wavefront per workgroup, two elements per pass
     const dim3 grid(unsigned(std::min<int64_t>((m.n_ele + 1) / 2, 256 * 8))), block(64);
-    if (m.kinem == 0)
+    a.ele_mat = m.ele_mat;
+    if (m.ele_mat)
+    {
+      if (m.kinem == 0)
+        hipLaunchKernelGGL((h27_diag_kernel<0, true>), grid, block, 0, stream, a);
+      else
+        hipLaunchKernelGGL((h27_diag_kernel<1, true>), grid, block, 0, stream, a);
+    }
+    else if (m.kinem == 0)
       hipLaunchKernelGGL((h27_diag_kernel<0>), grid, block, 0, stream, a);
     else
       hipLaunchKernelGGL((h27_diag_kernel<1>), grid, block, 0, stream, a);

@@ -30,6 +30,13 @@ struct DeviceMesh {
   double lambda = 0, mu = 0, cdiag = 0;  // StVK: C_00 = cdiag, C_01 = lambda, C_33 = mu
   int material = FCG_MAT_STVK;
   double nh_c = 0, nh_beta = 0;          // ElastHyper/CoupNeoHooke constants
+  // Per-element material constants (fcg_set_element_materials), NULL = the uniform ones above:
+  // [n_ele][4] = lambda, mu, cdiag, 0 (StVK) or nh_c, nh_beta, 0, 0 (CoupNeoHooke), one 32-byte
+  // record per element in the order the path's kernels walk the elements -- column-element order,
+  // FCG_PATH_GATHER: storage-slot (Morton) order, ele_mat[slot] belongs to element ele_orig[slot].
+  // The kernels that honour it are separate instantiations (template parameter TAB).
+  double* ele_mat = nullptr;
+  int32_t n_mat = 0;
 
   int32_t* ele_nodes = nullptr;     // [n_ele][npe]
   int32_t* ele_gid = nullptr;       // [n_ele]

@@ -325,6 +325,9 @@ struct ElementArgs {
   const int64_t* rowptr;
   double* K;
   double* fint;
+  // TAB instantiations (fcg_set_element_materials): [n_ele][4] lambda, mu, cdiag, 0 (StVK) or
+  // nh_c, nh_beta, 0, 0 (CoupNeoHooke) of each column element, instead of the uniform ones above
+  const double* ele_mat;
 };
 
 // Colour-ordered direct assembly: is element e (first-touch bits ft, see build_colored_plan in
@@ -349,7 +352,7 @@ __device__ inline bool first_touch27(const uint8_t* loc, uint32_t ft, int a, int
 // 1 / 2 = colour-ordered direct assembly, ACCUMULATE / OVERWRITE (hex27 lattice path).
 // Total Lagrangean kinematics with ElastHyper/CoupNeoHooke only (fcg_create enforces the pairing);
 // StVK runs in element_kernel_h8 and fcg_hex27.hip.
-template <int NPE, int BLOCK, int ASM = 0>
+template <int NPE, int BLOCK, int ASM = 0, bool TAB = false>
 __global__ __launch_bounds__(BLOCK, 1) void element_kernel(ElementArgs A)
 {
   constexpr int NGP = NPE;
@@ -603,7 +606,10 @@ __global__ __launch_bounds__(BLOCK, 1) void element_kernel(ElementArgs A)
       Ms[4] = F[1] * F[2] + F[4] * F[5] + F[7] * F[8];
       Ms[5] = F[2] * F[0] + F[5] * F[3] + F[8] * F[6];
       // So3Material::evaluate of ElastHyper: S and cmat
-      neohooke_stress_cmat(A.nh_c, A.nh_beta, E, sh.S + 6 * g, sh.Cm + 36 * g);
+      if constexpr (TAB)
+        neohooke_stress_cmat(A.ele_mat[4 * e], A.ele_mat[4 * e + 1], E, sh.S + 6 * g, sh.Cm + 36 * g);
+      else
+        neohooke_stress_cmat(A.nh_c, A.nh_beta, E, sh.S + 6 * g, sh.Cm + 36 * g);
     }
     __syncthreads();
     EL_STAMP(3);
@@ -858,7 +864,7 @@ __global__ __launch_bounds__(BLOCK, 1) void element_kernel(ElementArgs A)
 // (fcg_hex8_element.hpp); K_ab goes to the record of incidence (e,a), K_ab^T to (e,b).
 constexpr int H8_EPB = 32;  // elements per block
 
-template <int KIN>
+template <int KIN, bool TAB = false>
 __global__ __launch_bounds__(256) void element_kernel_h8(ElementArgs A)
 {
   constexpr int REC = 9 * 8 + 3;
@@ -880,6 +886,9 @@ __global__ __launch_bounds__(256) void element_kernel_h8(ElementArgs A)
   {
     const int64_t e = e0 + le;
     const bool active = e < A.n_ele;
+    StVK me = mat;
+    if constexpr (TAB)
+      if (active) me = StVK{A.ele_mat[4 * e], A.ele_mat[4 * e + 1], A.ele_mat[4 * e + 2]};
     if (active)
     {
       const int node = A.ele_nodes[e * 8 + j];
@@ -895,7 +904,7 @@ __global__ __launch_bounds__(256) void element_kernel_h8(ElementArgs A)
     __syncthreads();
     if (active)
     {
-      const int b = h8_stage_a<KIN>(j, s, dN, dNn, c_w8[j], mat);
+      const int b = h8_stage_a<KIN>(j, s, dN, dNn, c_w8[j], me);
       if (b) atomicMax(&bad[le], b);
     }
     __syncthreads();
@@ -903,7 +912,7 @@ __global__ __launch_bounds__(256) void element_kernel_h8(ElementArgs A)
     {
       const int a = j;
       double K[5][9], f[3];
-      h8_stage_b<KIN>(a, s, mat, A.want_k != 0, K, f);
+      h8_stage_b<KIN>(a, s, me, A.want_k != 0, K, f);
       const int32_t* inc = A.inc_of + e * 8;
       const int32_t ia = inc[a];
       if (ia >= 0)
@@ -1189,20 +1198,39 @@ hipError_t launch_element(const DeviceMesh& m, const double* d_u_col, bool want_
   a.stamps = m.stamps;
   a.nh_c = m.nh_c;
   a.nh_beta = m.nh_beta;
+  a.ele_mat = m.ele_mat;
+  const bool tab = m.ele_mat != nullptr;  // fcg_set_element_materials: the TAB instantiations
   if (m.material == FCG_MAT_ELASTHYPER_COUPNEOHOOKE)
   {
     // general constitutive tangent: one workgroup per element (TotLag only, checked at create)
     if (m.npe == 8)
-      hipLaunchKernelGGL((element_kernel<8, 64>), dim3(grid_for(m.n_ele, 256 * 32)), dim3(64), 0,
-          stream, a);
+    {
+      const dim3 grid(grid_for(m.n_ele, 256 * 32));
+      if (tab)
+        hipLaunchKernelGGL((element_kernel<8, 64, 0, true>), grid, dim3(64), 0, stream, a);
+      else
+        hipLaunchKernelGGL((element_kernel<8, 64>), grid, dim3(64), 0, stream, a);
+    }
     else
-      hipLaunchKernelGGL((element_kernel<27, 256>), dim3(grid_for(m.n_ele, 256 * 8)), dim3(256), 0,
-          stream, a);
+    {
+      const dim3 grid(grid_for(m.n_ele, 256 * 8));
+      if (tab)
+        hipLaunchKernelGGL((element_kernel<27, 256, 0, true>), grid, dim3(256), 0, stream, a);
+      else
+        hipLaunchKernelGGL((element_kernel<27, 256>), grid, dim3(256), 0, stream, a);
+    }
     return hipGetLastError();
   }
   if (m.npe != 8) return hipErrorInvalidValue;  // hex27 StVK has its own kernels
   const int grid = grid_for((m.n_ele + H8_EPB - 1) / H8_EPB, 256 * 16);
-  if (m.kinem == 0)
+  if (tab)
+  {
+    if (m.kinem == 0)
+      hipLaunchKernelGGL((element_kernel_h8<0, true>), dim3(grid), dim3(256), 0, stream, a);
+    else
+      hipLaunchKernelGGL((element_kernel_h8<1, true>), dim3(grid), dim3(256), 0, stream, a);
+  }
+  else if (m.kinem == 0)
     hipLaunchKernelGGL((element_kernel_h8<0>), dim3(grid), dim3(256), 0, stream, a);
   else
     hipLaunchKernelGGL((element_kernel_h8<1>), dim3(grid), dim3(256), 0, stream, a);

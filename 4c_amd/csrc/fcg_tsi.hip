@@ -858,6 +858,13 @@ int fcg_tsi_evaluate_fused(fcg_ctx* sctx, fcg_tsi_ctx* ctx, int mode, const doub
   fcg::TsiDevice& d = ctx->d;
   const fcg::DeviceMesh& m = sctx->mesh;
   auto rel_eq = [](double a, double b) { return std::fabs(a - b) <= 1e-14 * std::fabs(b); };
+  if (m.n_mat > 0)
+  {
+    ctx->last_error =
+        "fused TSI takes one material: the structural context carries per-element materials "
+        "(fcg_set_element_materials)";
+    return FCG_ERR_ARG;
+  }
   if (m.path != FCG_PATH_STRUCTURED || m.kinem != 0 || m.material != FCG_MAT_STVK || m.npe != 8 ||
       !d.fusable || sctx->device != ctx->device || m.n_node != d.n_node || m.n_ele != d.n_ele ||
       m.n_rows != d.n_rows_s || m.n_cols != d.n_cols_s || m.nnz != 9 * d.nnz_tt ||

@@ -133,7 +133,7 @@ EXPORTS = ["fcg_create", "fcg_destroy", "fcg_last_error", "fcg_evaluate", "fcg_e
            "fcg_device_alloc", "fcg_device_free", "fcg_memcpy_h2d", "fcg_memcpy_d2h",
            "fcg_memset_device", "fcg_set_timing", "fcg_get_timing", "fcg_get_info",
            "fcg_get_diagnostics", "fcg_get_create_phases", "fcg_measure_peaks", "fcg_measure_hbm", "fcg_spmv", "fcg_dirichlet_apply",
-           "fcg_pcg_solve", "fcg_spmv_f32", "fcg_tangent_apply", "fcg_tangent_diag", "fcg_box_stencil_apply", "fcg_box_transfer", "fcg_block_jacobi_setup", "fcg_block_jacobi_apply", "fcg_chebyshev_step", "fcg_node_transfer",
+           "fcg_pcg_solve", "fcg_spmv_f32", "fcg_tangent_apply", "fcg_tangent_diag", "fcg_set_element_materials", "fcg_box_stencil_apply", "fcg_box_transfer", "fcg_block_jacobi_setup", "fcg_block_jacobi_apply", "fcg_chebyshev_step", "fcg_node_transfer",
            "fcg_neumann_surface", "fcg_neumann_volume",
            "fcg_graph_build_device", "fcg_get_graph",
            "fcg_tsi_create", "fcg_tsi_destroy", "fcg_tsi_last_error", "fcg_tsi_evaluate_device",
@@ -198,6 +198,8 @@ def lib():
     L.fcg_get_diagnostics.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]
     if hasattr(L, "fcg_get_create_phases"):  # absent from older A/B builds (FCG_LIB)
         L.fcg_get_create_phases.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.c_int]
+    if hasattr(L, "fcg_set_element_materials"):  # absent from older A/B builds (FCG_LIB)
+        L.fcg_set_element_materials.argtypes = [vp, ctypes.c_int32, _dp, _dp, _i32p]
     L.fcg_spmv.argtypes = [vp, vp, vp, vp, vp]
     L.fcg_measure_peaks.argtypes = [ctypes.c_int, _dp, _dp, _dp]
     L.fcg_measure_hbm.argtypes = [ctypes.c_int, _dp, _dp]
@@ -663,6 +665,40 @@ class Evaluator:
         info = FcgInfo()
         L.fcg_get_info(h, ctypes.byref(info))
         self.info = info
+        self._n_materials = 0
+
+    @property
+    def n_materials(self):
+        """Entries of the per-element material table in force (0: the uniform material)."""
+        return self._n_materials
+
+    def set_element_materials(self, youngs, poisson=None, ele_mat=None):
+        """fcg_set_element_materials: element e (column-element order) takes youngs[ele_mat[e]],
+        poisson[ele_mat[e]] of the context's material kind; set_element_materials(None) returns to
+        the uniform material.  Honoured on PATH_GATHER / PATH_GENERAL (evaluate, tangent_apply,
+        tangent_diag); a PATH_STRUCTURED / PATH_COLORED context raises FcgError (code 3), as do
+        parameters outside the ranges of fcg_create -- the context then stays as it was.  Waits for
+        the context's stream; not to be called while evaluates run on other streams."""
+        L = lib()
+        if youngs is None:
+            rc = L.fcg_set_element_materials(self._h, 0, None, None, None)
+            n = 0
+        else:
+            E = np.ascontiguousarray(youngs, dtype=np.float64).ravel()
+            nu = None if poisson is None else np.ascontiguousarray(poisson, dtype=np.float64).ravel()
+            em = None if ele_mat is None else np.ascontiguousarray(ele_mat, dtype=np.int32).ravel()
+            if nu is not None and nu.size != E.size:
+                raise ValueError("youngs and poisson differ in length")
+            if em is not None and em.size != self.info.n_ele:
+                raise ValueError(f"ele_mat has {em.size} entries, the context {self.info.n_ele} elements")
+            n = int(E.size)
+            rc = L.fcg_set_element_materials(
+                self._h, n, _np_ptr(E, _dp), _np_ptr(nu, _dp) if nu is not None else None,
+                _np_ptr(em, _i32p) if em is not None else None)
+        if rc != 0:
+            self._raise(rc, -1)
+        self._n_materials = n
+        L.fcg_get_info(self._h, ctypes.byref(self.info))  # device_bytes counts the table
 
     def graph(self):
         """fcg_get_graph: (rowptr int64, col_lid int32) host copies of the context's CSR graph --

@@ -654,7 +654,13 @@ class Multigrid(CycleFCG):
     """Flexible-CG solver preconditioned by a geometric multigrid V-cycle (see module doc).
 
     fine_mesh / fine_ev: the discretisation being solved (BoxMesh + Evaluator, single rank);
-    dbc_nodes(mesh) -> bool mask of the clamped nodes of a mesh of the same box (all 3 DOFs)."""
+    dbc_nodes(mesh) -> bool mask of the clamped nodes of a mesh of the same box (all 3 DOFs).
+
+    youngs / poisson: the one material of the rediscretised coarse levels.  A fine evaluator that
+    carries per-element materials (Evaluator.set_element_materials) keeps its exact fine operator,
+    diagonal blocks and residual, but the coarse levels stay homogeneous in (youngs, poisson): for
+    a heterogeneous fine level the V-cycle is a weaker, still valid preconditioner (more FCG
+    iterations, the same solution)."""
 
     def __init__(self, fine_mesh, fine_ev, dbc_nodes, youngs, poisson, nu=2, min_intervals=4,
                  max_levels=8, ratio=10.0, boost=1.1, coarse_rtol=1e-2, coarse_max_iter=2000,

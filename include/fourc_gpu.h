@@ -129,6 +129,24 @@ int fcg_destroy(fcg_ctx* ctx);
 /* Text of the last error on this context (or of the last failed fcg_create when ctx == NULL). */
 const char* fcg_last_error(const fcg_ctx* ctx);
 
+/* Per-element material parameters (a discretization with several MAT ids of one kind, as
+ * Solid::evaluate asks each element's So3Material): element e (column-element order of
+ * desc->ele_nodes) takes youngs[ele_mat[e]], poisson[ele_mat[e]] of the context's fcg_material.
+ * Host arrays, copied.  n_mat = 0 (arrays NULL) returns to the uniform material of fcg_create.
+ * Checks as fcg_create's (youngs > 0, poisson in [-1, 0.5), 0 <= ele_mat[e] < n_mat); a violation
+ * returns FCG_ERR_ARG, fcg_last_error names the offending entry and the context stays as it was.
+ * The constants are formed per material with fcg_create's host arithmetic and stored per element on
+ * the device (32 bytes per element, counted in fcg_info.device_bytes), so a table whose entries
+ * all equal the context's own material reproduces the uniform results bit for bit.
+ * Honoured by the FCG_PATH_GATHER and FCG_PATH_GENERAL kernels (hex8 and hex27, both kinematics,
+ * both materials) and by fcg_tangent_apply / fcg_tangent_diag.  A context on FCG_PATH_STRUCTURED
+ * or FCG_PATH_COLORED refuses a table with FCG_ERR_ARG (create it with FCG_PATH_GATHER /
+ * FCG_PATH_GENERAL), and fcg_tsi_evaluate_fused refuses a structural context that carries one.
+ * The call drains the context's stream before it swaps the tables; it must not run concurrently
+ * with evaluates of the context on other streams. */
+int fcg_set_element_materials(fcg_ctx* ctx, int32_t n_mat, const double* youngs,
+    const double* poisson, const int32_t* ele_mat);
+
 /*
  * Discretization::evaluate on host buffers (blocking, reference semantics):
  *   u_col    [n_cols]   displacement column vector (Discretization::set_state("displacement"))
