@@ -2470,6 +2470,12 @@ int fcg_amg_create(fcg_ctx* ctx, const int64_t* rowptr, const int32_t* col_lid,
     ctx->last_error = "fcg_amg_create: 3 DOFs per owned node (rows 3b..3b+2), owned columns first";
     return FCG_ERR_ARG;
   }
+  if (!m.triple_rows)
+  {
+    // the block copies of K (node_csr_to_bsr_kernel, perm_csr_to_bsr_kernel) read a row by triples
+    ctx->last_error = "fcg_amg_create: a row of the context holds columns that are not node DOF triples";
+    return FCG_ERR_ARG;
+  }
   fcg_amg* h = new fcg_amg();
   h->ctx = ctx;
   h->device = ctx->device;

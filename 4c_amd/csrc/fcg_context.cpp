@@ -1077,6 +1077,10 @@ int fcg_create(const fcg_desc* d, fcg_ctx** out)
       return FCG_ERR_ARG;
     }
   }
+  // whether every node row holds node DOF triples (c, c + 1, c + 2) only: the node-row SpMV and the
+  // AMG's block copy walk a row by triples; a caller's graph may hold other columns as well (the
+  // general path assembles it all the same), and then the operator goes row by row
+  std::atomic<bool> triple_rows{true};
   parallel_for(nrn, [&](int64_t r) {
     const int64_t s = d->rowptr[row0[r]];
     const int64_t len = d->rowptr[row0[r] + 1] - s;
@@ -1086,6 +1090,11 @@ int fcg_create(const fcg_desc* d, fcg_ctx** out)
         std::lock_guard<std::mutex> lk(err_m);
         err = "the 3 rows of a node must share one column pattern";
       }
+    const int32_t* c = d->col_lid + s;
+    bool triples = len % 3 == 0;
+    for (int64_t j = 0; triples && j < len; j += 3)
+      triples = c[j + 1] == c[j] + 1 && c[j + 2] == c[j] + 2;
+    if (!triples) triple_rows.store(false, std::memory_order_relaxed);
   });
   if (!err.empty())
   {
@@ -1325,6 +1334,7 @@ int fcg_create(const fcg_desc* d, fcg_ctx** out)
     const bool rowcol = rowcol_ok.load();
     m.square_local = rowcol && d->n_rows == d->n_cols;
     m.owned_cols_first = rowcol;
+    m.triple_rows = triple_rows.load();
     chk(upload_big(&m.col_lid, d->col_lid, m.nnz));
     chk(upload(&m.diag_pos, diag.data(), d->n_rows, bytes));
   }

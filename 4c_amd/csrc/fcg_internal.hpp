@@ -124,6 +124,7 @@ struct DeviceMesh {
   int64_t* diag_pos = nullptr;      // [n_rows] position of the diagonal entry in K values, -1 = none
   bool square_local = false;        // matrix column map == row map (single rank)
   bool owned_cols_first = false;    // column LID of every owned DOF == its row LID (ghosts after)
+  bool triple_rows = true;          // every node row is made of DOF triples (c, c+1, c+2) only
   double* pcg_work = nullptr;       // PCG vectors and partial sums (allocated on first solve)
   int64_t pcg_n = 0;
 };

@@ -47,9 +47,11 @@ __device__ inline double block_sum(double v, double* sbuf)
   return t;
 }
 
-// y = K x by node rows: the 3 rows of an owned node share one column pattern made of DOF triples
-// (checked by fcg_create), so LPN lanes walk the node's neighbour triples -- one column index,
-// x[c..c+2] and the 3 x 3 block of the 3 rows per triple -- instead of one index per matrix entry.
+// y = K x by node rows: the 3 rows of an owned node share one column pattern (checked by
+// fcg_create) and, on the contexts this kernel is launched for (DeviceMesh::triple_rows, recorded
+// by fcg_create), that pattern is made of DOF triples only, so LPN lanes walk the node's neighbour
+// triples -- one column index, x[c..c+2] and the 3 x 3 block of the 3 rows per triple -- instead of
+// one index per matrix entry.  A context whose rows hold other columns too takes spmv_row_kernel.
 // Row-major sums in a fixed lane order: deterministic.  Optionally
 // partial[blockIdx] = sum over the block's rows of dotw[row] * y[row].  V = float: matrix values
 // stored in FP32 (the multigrid smoother's copy of K), vectors and sums in FP64.
@@ -106,6 +108,27 @@ __global__ __launch_bounds__(kBlock) void spmv_node_kernel(const int64_t* __rest
     const double t = block_sum(mine, sbuf);
     if (threadIdx.x == 0) partial[blockIdx.x] = t;
   }
+}
+
+// y = K x row by row, for a context whose node rows hold columns besides node DOF triples (a
+// caller's graph with extra couplings; fcg_create accepts it and the general path assembles it):
+// LPR lanes stride over one row's entries, summed in a fixed lane order -- deterministic.  Every
+// row of the row map is written, a row without entries as 0.
+constexpr int kLanesPerRow = 16;
+template <typename V>
+__global__ __launch_bounds__(kBlock) void spmv_row_kernel(const int64_t* __restrict__ rowptr,
+    const int32_t* __restrict__ col, const V* __restrict__ vals, const double* __restrict__ x,
+    double* __restrict__ y, int64_t n_rows)
+{
+  constexpr int LPR = kLanesPerRow;
+  const int lane = threadIdx.x % LPR;
+  const int64_t row = (int64_t(blockIdx.x) * kBlock + threadIdx.x) / LPR;
+  double a = 0.0;
+  if (row < n_rows)
+    for (int64_t j = rowptr[row] + lane; j < rowptr[row + 1]; j += LPR) a += double(vals[j]) * x[col[j]];
+#pragma unroll
+  for (int o = LPR / 2; o >= 1; o >>= 1) a += __shfl_xor(a, o, LPR);
+  if (row < n_rows && lane == 0) y[row] = a;
 }
 
 // Single-block reduction of n partials (fixed order) into sc[slot]; then the scalar recurrences
@@ -537,7 +560,15 @@ hipError_t launch_spmv(const DeviceMesh& m, const V* K, const double* x, double*
     const double* dotw, double* partial, hipStream_t s)
 {
   if (m.n_rows == 0) return hipSuccess;
-  // node rows (every owned row belongs to a node triple, fcg_create checks the pattern)
+  if (!m.triple_rows)
+  {
+    // rows with columns that are no node DOF triples: the scalar-row kernel (no dot partials)
+    if (partial) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((spmv_row_kernel<V>), dim3(blocks_for(m.n_rows * kLanesPerRow, kBlock)),
+        dim3(kBlock), 0, s, m.rowptr, m.col_lid, K, x, y, m.n_rows);
+    return hipGetLastError();
+  }
+  // node rows of DOF triples (every owned row belongs to a node triple, fcg_create checks both)
   if (m.npe == 27)
     hipLaunchKernelGGL((spmv_node_kernel<64, V>), dim3(spmv_grid(m, 64, partial != nullptr)),
         dim3(kBlock), 0, s, m.rowptr, m.rownode_row0, m.col_lid, K, x, y, m.n_rownodes, dotw,
@@ -878,9 +909,11 @@ int fcg_pcg_solve(fcg_ctx* ctx, const double* d_K_vals, const double* d_b_row, d
 
 int fcg_block_jacobi_setup(fcg_ctx* ctx, const double* d_K_vals, double* d_dinv, void* stream)
 {
-  if (!ctx || !d_K_vals || !d_dinv) return FCG_ERR_ARG;
+  if (!ctx) return FCG_ERR_ARG;
   fcg::DeviceMesh& m = ctx->mesh;
   const int64_t nn = m.n_rownodes;
+  if (nn == 0 && m.n_rows == 0) return FCG_OK;  // a rank without rows: nothing to invert
+  if (!d_K_vals || !d_dinv) return FCG_ERR_ARG;
   if (3 * nn != m.n_rows)
   {
     ctx->last_error = "fcg_block_jacobi_setup: every owned row must belong to an owned node's DOF triple";
@@ -916,10 +949,11 @@ int fcg_block_jacobi_setup(fcg_ctx* ctx, const double* d_K_vals, double* d_dinv,
 int fcg_block_jacobi_apply(fcg_ctx* ctx, const double* d_dinv, const double* d_r_row, double* d_z_row,
     double scale, int accumulate, void* stream)
 {
-  if (!ctx || !d_dinv || !d_r_row || !d_z_row) return FCG_ERR_ARG;
+  if (!ctx) return FCG_ERR_ARG;
   fcg::DeviceMesh& m = ctx->mesh;
   const int64_t nn = m.n_rownodes;
-  if (nn == 0) return FCG_OK;
+  if (nn == 0) return FCG_OK;  // a rank without rows (its empty buffers may be NULL)
+  if (!d_dinv || !d_r_row || !d_z_row) return FCG_ERR_ARG;
   (void)hipSetDevice(ctx->device);
   hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
   hipLaunchKernelGGL(fcg::bj_apply_kernel, dim3(fcg::blocks_for(nn, fcg::kBlock)), dim3(fcg::kBlock), 0, s,
@@ -936,11 +970,11 @@ int fcg_block_jacobi_apply(fcg_ctx* ctx, const double* d_dinv, const double* d_r
 int fcg_chebyshev_step(fcg_ctx* ctx, const double* d_dinv, const double* d_b_row, const double* d_y_row,
     double* d_d_row, double* d_x_row, double c_d, double c_r, int mode, void* stream)
 {
-  if (!ctx || !d_dinv || !d_b_row || (!d_y_row && mode != 2) || !d_d_row || !d_x_row || mode < 0 || mode > 2)
-    return FCG_ERR_ARG;
+  if (!ctx || mode < 0 || mode > 2) return FCG_ERR_ARG;
   fcg::DeviceMesh& m = ctx->mesh;
   const int64_t nn = m.n_rownodes;
-  if (nn == 0) return FCG_OK;
+  if (nn == 0) return FCG_OK;  // a rank without rows (its empty buffers may be NULL)
+  if (!d_dinv || !d_b_row || (!d_y_row && mode != 2) || !d_d_row || !d_x_row) return FCG_ERR_ARG;
   (void)hipSetDevice(ctx->device);
   hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
   hipLaunchKernelGGL(fcg::cheb_step_kernel, dim3(fcg::blocks_for(nn, fcg::kBlock)), dim3(fcg::kBlock), 0, s,

@@ -119,7 +119,8 @@ class StaticNewton:
         self.nnz = int(info.nnz)
         f64 = dict(dtype=torch.float64, device=self.dev)
         self.fext = torch.as_tensor(np.asarray(fext_row, dtype=np.float64)).to(self.dev)
-        self.dbc = torch.as_tensor(np.asarray(dbc_rows, dtype=np.int32)).to(self.dev)
+        # fcg_dirichlet_apply wants distinct rows (two clamped faces concatenated share an edge)
+        self.dbc = torch.as_tensor(np.unique(np.asarray(dbc_rows, dtype=np.int32))).to(self.dev)
         self.assemble_tangent = bool(assemble_tangent)
         if not self.assemble_tangent and getattr(linear_solver, "needs_matrix", True) is not False:
             raise ValueError("assemble_tangent=False needs a linear_solver whose needs_matrix is "

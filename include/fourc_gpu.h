@@ -241,13 +241,19 @@ int fcg_get_create_phases(const fcg_ctx* ctx, double* out, int n);
  * the stream has drained.
  * ---------------------------------------------------------------------------------------- */
 /* y_row = K x_col (Epetra_CrsMatrix::Multiply on the owned rows).  Asynchronous: queued on
- * `stream` (NULL: the context's stream), which orders it with the caller's later work. */
+ * `stream` (NULL: the context's stream), which orders it with the caller's later work.  Right on
+ * every graph fcg_create accepts: node rows made of DOF triples only go triple by triple, a graph
+ * with other columns as well (a caller's extra couplings) goes row by row.  A context without
+ * rows is a no-op (FCG_OK, the buffers may be NULL), here and in the calls below. */
 int fcg_spmv(fcg_ctx* ctx, const double* d_K_vals, const double* d_x_col, double* d_y_row,
     void* stream);
 /* Dirichlet rows (row LIDs d_rows[n_dbc], device array): freact[row] = -rhs[row] (if freact is not
  * NULL, Solid::Dbc::extract_freact: with rhs = F = f_int - f_ext the reaction is f_ext - f_int), rhs[row] = 0 (apply_dirichlet_to_system with zeros),
  * K row -> unit row (SparseMatrix::apply_dirichlet, diagonalblock = true,
- * 4C_linalg_sparsematrix.cpp:978-1097).  K or rhs may be NULL. */
+ * 4C_linalg_sparsematrix.cpp:978-1097).  K or rhs may be NULL.  The rows of d_rows must be
+ * distinct: a row listed twice is handled by two wavefronts in no fixed order, and the second may
+ * read the rhs the first already zeroed (freact = -0.0).  A row LID outside [0, n_rows) or a row
+ * without a diagonal entry gives FCG_ERR_ARG; the other rows listed are still applied. */
 int fcg_dirichlet_apply(fcg_ctx* ctx, int64_t n_dbc, const int32_t* d_rows, double* d_K_vals,
     double* d_rhs_row, double* d_freact_row, void* stream);
 /* K x = b by CG preconditioned with the inverse 3x3 nodal diagonal blocks (block Jacobi) from x = 0 until |r| <= rtol |b| or max_iter iterations;
@@ -277,7 +283,10 @@ int fcg_pcg_solve(fcg_ctx* ctx, const double* d_K_vals, const double* d_b_row, d
  * fcg_node_transfer: y[dst_row0[o] + d] = (accumulate ? y : 0) + sum_{j in [ptr[o], ptr[o+1])}
  * w[j] x[src_row0[j] + d] for d = 0..2 and dst_row0[o] >= 0 (all device arrays; stream may be
  * NULL: the context's stream for the ctx calls, the null stream for fcg_node_transfer).
- * Asynchronous on `stream` except fcg_block_jacobi_setup, which returns after it drained. */
+ * Asynchronous on `stream` except fcg_block_jacobi_setup, which returns after it drained.
+ * On a context without rows (a rank that owns none) fcg_block_jacobi_setup, fcg_block_jacobi_apply
+ * and fcg_chebyshev_step return FCG_OK before they look at their pointers, as fcg_spmv does: the
+ * rank's empty buffers may be NULL. */
 int fcg_block_jacobi_setup(fcg_ctx* ctx, const double* d_K_vals, double* d_dinv, void* stream);
 int fcg_block_jacobi_apply(fcg_ctx* ctx, const double* d_dinv, const double* d_r_row, double* d_z_row,
     double scale, int accumulate, void* stream);
@@ -395,7 +404,8 @@ int fcg_bsr_to_dense(int device, int b, int64_t n_brows, const int64_t* d_ptr, c
  * calls instead of its Belos CG + MueLu preconditioner on a tangent the context assembled.
  * fcg_amg_create: the context's own CSR graph (host rowptr / col_lid as in fcg_desc; rows 3b..3b+2
  * = the DOFs of block row b, single rank), node_x[b][3] the reference coordinates of block row b's
- * node, the Dirichlet rows (unit rows of K); builds the hierarchy's patterns on the host.
+ * node, the Dirichlet rows (unit rows of K); builds the hierarchy's patterns on the host.  A
+ * context whose rows hold columns that are not node DOF triples is refused (FCG_ERR_ARG).
  * fcg_amg_solve: numeric setup for d_K_vals (the tangent after fcg_dirichlet_apply) and flexible
  * CG with one V-cycle per iteration from x = 0 to |r| <= rtol |b|; returns FCG_ERR_SINGULAR when
  * the V-cycle turns indefinite or the iteration diverges.  fcg_amg_level_info: DOFs, blocks and
