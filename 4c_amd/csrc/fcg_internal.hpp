@@ -8,6 +8,7 @@
 #include <string>
 #include <vector>
 
+#include "fcg_create_plan.hpp"  // PLANE_REC_WORDS, the host plan structs
 #include "fourc_gpu.h"
 
 namespace fcg {
@@ -128,10 +129,6 @@ struct DeviceMesh {
   double* pcg_work = nullptr;       // PCG vectors and partial sums (allocated on first solve)
   int64_t pcg_n = 0;
 };
-
-// One record per (tile, node plane): row0[16] | rowlen[16] | rbase[16] (int64) | npos[16][27]
-// (uint16, column position of lattice neighbour t inside the node's rows, 0xFFFF = absent).
-constexpr int PLANE_REC_WORDS = 288;
 
 // Launches the structured hex8 row-block sweep (element evaluation + assembly, fcg_sweep.hip).
 hipError_t launch_sweep_h8(const DeviceMesh& m, const double* d_u_col, bool want_k,

@@ -29,6 +29,21 @@ def test_integration_builds_and_reports_missing_device():
     assert "PASS" in p.stdout
 
 
+PLAN_CHECK = os.path.join(CXX, "_build", "create_plan_check")
+
+
+def test_create_plans_match_connectivity_on_cpu():
+    """fcg_create's host plans (tests/cxx/create_plan_check.cpp: g++ alone, the plan unit and the
+    box-mesh builder, no libfourc_gpu): the gather records and tmap nibbles, the hex27 slab ring
+    and the slab-size rule, checked against the connectivity of small permuted, partitioned,
+    doubled-element and lone-node meshes."""
+    if not os.path.exists(PLAN_CHECK):
+        subprocess.run(["make", "-s", "-C", CXX], check=True)
+    p = subprocess.run([PLAN_CHECK], capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0, p.stdout + p.stderr
+    assert "PASS" in p.stdout
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("args", [["6", "5", "4", "2"], ["9", "7", "8", "3"], ["5", "5", "5", "1"]])
 def test_integration_on_device(args):
