@@ -44,7 +44,7 @@ hipError_t upload(T** dst, const T* src, int64_t n, int64_t& bytes)
 
 void free_mesh(fcg::DeviceMesh& m)
 {
-  void* ptrs[] = {m.ele_mat, m.apply_ye, m.apply_dof, m.diag_de, m.diag_dbc, m.gather_dummy, m.multi_ptr, m.rec_row0, m.rec_meta, m.rec_base, m.rec_ele, m.rec_a, m.rec_tmap, m.ele_orig, m.inc_ele, m.inc_a, m.asm_order, m.ele_x,
+  void* ptrs[] = {m.node_dof_row, m.node_dof_kcol, m.mass_ptr, m.mass_inc, m.mass_tab, m.mass_rho, m.mass_bad, m.ele_mat, m.apply_ye, m.apply_dof, m.diag_de, m.diag_dbc, m.gather_dummy, m.multi_ptr, m.rec_row0, m.rec_meta, m.rec_base, m.rec_ele, m.rec_a, m.rec_tmap, m.ele_orig, m.inc_ele, m.inc_a, m.asm_order, m.ele_x,
       m.ele_dof, m.ele_nodes, m.ele_gid, m.node_x, m.node_dof_col, m.inc_of, m.inc_ptr,
       m.rownode_row0, m.inc_pos, m.rowptr, m.scratch, m.err, m.elem_at, m.lat_x, m.lat_dof,
       m.plane_rec,
@@ -247,6 +247,9 @@ void upload_common(Uploader& U, const fcg_desc* d, const plan::NodeRows& N, int6
   U.up(&m.ele_gid, d->ele_gid ? d->ele_gid : eg.data(), d->n_ele);
   U.up(&m.node_x, d->node_x, d->n_node * 3);
   U.up(&m.node_dof_col, d->node_dof_col, d->n_node);
+  // the path-independent node -> row map and matrix-column LIDs the mass kernels need
+  U.up(&m.node_dof_row, d->node_dof_row, d->n_node);
+  if (d->node_dof_kcol) U.up(&m.node_dof_kcol, d->node_dof_kcol, d->n_node);
   U.up(&m.rownode_row0, N.row0);
   U.up_big(&m.rowptr, d->rowptr, d->n_rows + 1);
   // operator support: column LIDs, diagonal positions (the Dirichlet rows and the Jacobi

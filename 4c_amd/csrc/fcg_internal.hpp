@@ -128,6 +128,16 @@ struct DeviceMesh {
   bool triple_rows = true;          // every node row is made of DOF triples (c, c+1, c+2) only
   double* pcg_work = nullptr;       // PCG vectors and partial sums (allocated on first solve)
   int64_t pcg_n = 0;
+
+  // mass (fcg_mass.hip).  The node -> row map and the matrix-column LIDs are kept by fcg_create on
+  // every path (the sweep and the gather hold no inc_of); the plan is built on the first mass call.
+  int32_t* node_dof_row = nullptr;   // [n_node] row LID of the node's first DOF, -1 = not owned
+  int32_t* node_dof_kcol = nullptr;  // [n_node] matrix-column LID, NULL = node_dof_col
+  int64_t* mass_ptr = nullptr;       // [n_node+1] incidence range of each column node with a row
+  int64_t* mass_inc = nullptr;       // element * 32 + local node, ascending per node
+  double* mass_tab = nullptr;        // N | dN | w at the Gauss points of the stiffness rule
+  double* mass_rho = nullptr;        // [n_ele] per-element densities of the last call that gave them
+  int32_t* mass_bad = nullptr;       // [1] lowest column element with det J <= 0 at a Gauss point
 };
 
 // Launches the structured hex8 row-block sweep (element evaluation + assembly, fcg_sweep.hip).
@@ -211,6 +221,17 @@ hipError_t launch_h27_diag(const DeviceMesh& m, const double* d_u_col, int64_t n
 hipError_t gather_precompute(DeviceMesh& m, int64_t n_ele, hipStream_t stream);
 hipError_t launch_gather_h8(const DeviceMesh& m, const double* d_u_col, bool want_k, bool overwrite,
     double* d_K, double* d_fint, hipStream_t stream);
+// Mass (fcg_mass.hip).  mass_plan_build: the per-node incidence lists and the shape table, once
+// per context (bytes: added to the context's device_bytes; drains the stream).  launch_mass: one
+// wavefront per owned row node integrates its mass row into the CSR values (d_M), the compact
+// node form (d_m_node, nnz / 9) and / or the row sums (d_lumped); det J <= 0 at a Gauss point sets
+// the solver flag word and m.mass_bad.  launch_effective_tangent: K <- cK K + cM M in place
+// (cK == 0: K is not read) and / or y_row = M x_col from the compact form.
+hipError_t mass_plan_build(DeviceMesh& m, int64_t& bytes, hipStream_t stream);
+hipError_t launch_mass(const DeviceMesh& m, double density, const double* d_ele_density, double* d_M,
+    bool overwrite, double* d_m_node, double* d_lumped, hipStream_t stream);
+hipError_t launch_effective_tangent(const DeviceMesh& m, double cK, double cM, const double* d_m_node,
+    double* d_K, const double* d_x_col, double* d_y_row, hipStream_t stream);
 
 }  // namespace fcg
 

@@ -153,7 +153,8 @@ EXPORTS = ["fcg_create", "fcg_destroy", "fcg_last_error", "fcg_evaluate", "fcg_e
            "fcg_amg_levels", "fcg_amg_level_info", "fcg_amg_setup_ms", "fcg_amg_stats", "fcg_amg_last_error",
            "fcg_amg_destroy", "fcg_amg_setup", "fcg_amg_iterate", "fcg_amg_apply",
            "fcg_amg_coupled_levels", "fcg_amg_coupled_stats", "fcg_comm_exchange_device",
-           "fcg_transport_rccl", "fcg_dfcg_solve"]
+           "fcg_transport_rccl", "fcg_dfcg_solve",
+           "fcg_mass_assemble", "fcg_mass_nodal", "fcg_effective_tangent"]
 
 _lib = None
 FUNCT_FN = ctypes.CFUNCTYPE(ctypes.c_double, ctypes.c_int, _dp, ctypes.c_double, ctypes.c_void_p)
@@ -314,6 +315,9 @@ def lib():
     L.fcg_transport_rccl.argtypes = [ctypes.POINTER(FcgRcclPair), ctypes.POINTER(FcgTransport)]
     L.fcg_dfcg_solve.argtypes = [vp, vp, ctypes.POINTER(FcgTransport), vp, vp, vp, c_dbl, c_int, vp,
                                  ctypes.POINTER(c_int), _dp]
+    L.fcg_mass_assemble.argtypes = [vp, c_dbl, _dp, c_int, vp, vp]
+    L.fcg_mass_nodal.argtypes = [vp, c_dbl, _dp, vp, vp, vp]
+    L.fcg_effective_tangent.argtypes = [vp, c_dbl, c_dbl, vp, vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -827,6 +831,59 @@ class Evaluator:
         if rc != 0:
             self._raise(rc, -1)
         return it.value, rr.value
+
+    def _ele_density(self, ele_density):
+        if ele_density is None:
+            return None, None
+        rho = np.ascontiguousarray(ele_density, dtype=np.float64).ravel()
+        if rho.size != self.info.n_ele:
+            raise ValueError(f"ele_density has {rho.size} entries, the context {self.info.n_ele} elements")
+        return rho, _np_ptr(rho, _dp)
+
+    def _f64(self, n):
+        import torch
+        return torch.empty(int(n), dtype=torch.float64, device=torch.device("cuda", self.device))
+
+    def mass(self, density, ele_density=None, mode=OVERWRITE, out=None, stream=None):
+        """fcg_mass_assemble: the consistent mass on the context's CSR graph (4C's systemmatrix2 of
+        struct_calc_nlnstiffmass) into `out` ([nnz] device tensor; None: a new one, which
+        ACCUMULATE starts from zeros).  ele_density: one density per column element (host array),
+        `density` is then ignored.  Returns the tensor; the call waits for the stream."""
+        if out is None:
+            out = self._f64(self.info.nnz)
+            if mode == ACCUMULATE:
+                out.zero_()
+        rho, rp = self._ele_density(ele_density)
+        rc = lib().fcg_mass_assemble(self._h, float(density), rp, int(mode), _tensor_ptr(out),
+                                     self._stream(stream))
+        if rc != 0:
+            self._raise(rc, -1)
+        lib().fcg_get_info(self._h, ctypes.byref(self.info))  # device_bytes counts the mass plan
+        return out
+
+    def mass_nodal(self, density, ele_density=None, m_node=None, m_lumped=None, stream=None):
+        """fcg_mass_nodal: the compact node form ([nnz / 9], one double per row node and neighbour
+        node) and the row-sum lumped mass ([n_rows]).  With both None both are allocated; returns
+        (m_node, m_lumped), None for a form not asked for.  Waits for the stream."""
+        if m_node is None and m_lumped is None:
+            m_node, m_lumped = self._f64(self.info.nnz // 9), self._f64(self.info.n_rows)
+        rho, rp = self._ele_density(ele_density)
+        rc = lib().fcg_mass_nodal(self._h, float(density), rp, _tensor_ptr(m_node),
+                                  _tensor_ptr(m_lumped), self._stream(stream))
+        if rc != 0:
+            self._raise(rc, -1)
+        lib().fcg_get_info(self._h, ctypes.byref(self.info))
+        return m_node, m_lumped
+
+    def effective_tangent(self, cK, cM, m_node, K_vals=None, x_col=None, y_row=None, stream=None):
+        """fcg_effective_tangent: K_vals <- cK K_vals + cM M in place (cK == 0: K_vals is not read)
+        and, with x_col and y_row, y_row = M x_col in the same pass; m_node from mass_nodal.
+        Asynchronous."""
+        rc = lib().fcg_effective_tangent(self._h, float(cK), float(cM), _tensor_ptr(m_node),
+                                         _tensor_ptr(K_vals), _tensor_ptr(x_col), _tensor_ptr(y_row),
+                                         self._stream(stream))
+        if rc != 0:
+            self._raise(rc, -1)
 
     def set_timing(self, enable):
         lib().fcg_set_timing(self._h, 1 if enable else 0)

@@ -256,6 +256,42 @@ int fcg_spmv(fcg_ctx* ctx, const double* d_K_vals, const double* d_x_col, double
  * without a diagonal entry gives FCG_ERR_ARG; the other rows listed are still applied. */
 int fcg_dirichlet_apply(fcg_ctx* ctx, int64_t n_dbc, const int32_t* d_rows, double* d_K_vals,
     double* d_rhs_row, double* d_freact_row, void* stream);
+/* Inertia (DYNAMICTYPE GenAlpha; 4c_amd/dynamics.py).  The consistent mass block between nodes a
+ * and b of displacement-based solid elements is m_ab I_3,
+ *   m_ab = sum_e sum_g rho_e w_g det J_g N_a(xi_g) N_b(xi_g)
+ * on the element's stiffness Gauss rule (8 / 27 points; the 27-point rule's constants in full double
+ * precision, so that the total mass is rho V to rounding), J from the reference coordinates
+ * (struct_calc_nlnstiffmass, 4C_solid_3D_ele_calc.cpp; independent of kinematics and material).
+ * Every context fcg_create accepts, on every path; as in evaluate only owned rows are written and
+ * all column elements (ghosts included) contribute; columns are LIDs of the matrix column map.
+ * density > 0, or ele_density[e] > 0 per column element (host [n_ele], copied; density is then
+ * ignored): a violation returns FCG_ERR_ARG and fcg_last_error names the entry.  A Gauss point with
+ * det J <= 0 returns FCG_ERR_NODAL_DETJ through the solver flag word, as fcg_tangent_diag's
+ * errors (never evaluate's sticky flags), fcg_last_error names the element GID.  Each entry is
+ * summed over its elements in ascending column-element index, no atomics on doubles: two calls
+ * give the same bits.  A per-context plan (the nodes' element lists, counted in device_bytes) is
+ * built on the first mass call.  Both mass calls return after the stream has drained.
+ * fcg_mass_assemble: the CSR form on the context's graph (4C's systemmatrix2).  OVERWRITE writes
+ * every owned entry (exact 0 off the block diagonals and in columns that are no element node's),
+ * ACCUMULATE adds the block diagonals onto the caller's values. */
+int fcg_mass_assemble(fcg_ctx* ctx, double density, const double* ele_density /* host [n_ele] or NULL */,
+    int mode /* fcg_mode */, double* d_M_vals /* [nnz] */, void* stream);
+/* The compact node form and / or the row-sum lumped mass (4C's LUMPMASS); needs a context whose
+ * rows are all owned nodes' DOF triples (else FCG_ERR_ARG).  For the context's k-th row node (the
+ * block order of fcg_block_jacobi_setup) with first row row0, the entry of its t-th column triple
+ * -- columns col_lid[rowptr[row0] + 3 t .. + 2] -- is m_node[rowptr[row0] / 9 + t];
+ * m_lumped_row[r] = sum_b m_ab of r's node, the same value on the node's three rows. */
+int fcg_mass_nodal(fcg_ctx* ctx, double density, const double* ele_density,
+    double* d_m_node /* [nnz/9] or NULL */, double* d_m_lumped_row /* [n_rows] or NULL */, void* stream);
+/* K <- cK K + cM M in place and y_row = M x_col, in one pass over the node rows (the context
+ * requirement of fcg_mass_nodal): every stored entry becomes cK K[j], the three diagonal entries of
+ * each 3 x 3 block get fma(cM, m_ab, cK K[j]).  cK == 0: K is not read, the result is exactly
+ * cM M whatever the buffer held.  With d_x_col and d_y_row, y_row = M x_col in the same pass (sums
+ * in a fixed lane order: deterministic); d_K_vals NULL: only y.  All three NULL: FCG_ERR_ARG.
+ * Asynchronous on `stream` like fcg_spmv. */
+int fcg_effective_tangent(fcg_ctx* ctx, double cK, double cM, const double* d_m_node,
+    double* d_K_vals /* may be NULL */, const double* d_x_col, double* d_y_row /* both may be NULL */,
+    void* stream);
 /* K x = b by CG preconditioned with the inverse 3x3 nodal diagonal blocks (block Jacobi) from x = 0 until |r| <= rtol |b| or max_iter iterations;
  * single-rank systems only (matrix column map = row map), else FCG_ERR_ARG.  Deterministic. */
 /* y_row = K x_col with the matrix values stored in FP32 (vectors and sums FP64): the multigrid
