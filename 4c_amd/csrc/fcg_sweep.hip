@@ -141,7 +141,10 @@ struct SweepShared {
 #endif
   // (the thermal pass's 7 held values keep rows of 9: aligned rows of 10 measured +0.3 % on the
   // two-field tangent, r06_sweep_hold10_ab.txt)
-  alignas(16) double hold[TX * TY][9][TSI ? (TH ? 9 : 18) : kHs];
+  // Structural passes: one more column, never written after the prologue has zeroed it.  A lane
+  // whose block adds no held part reads its nine zeros, so that every lane of the wave adds what
+  // it read without a branch (see emit).
+  alignas(16) double hold[TX * TY + (TSI ? 0 : 1)][9][TSI ? (TH ? 9 : 18) : kHs];
 #endif
   // DEFER (rows not in lattice order): the blocks of node plane L+1's rows with the plane below
   // (dz = -1, finished in layer L) wait here and are written in layer L+1 beside the row's other
@@ -742,8 +745,10 @@ __global__ __launch_bounds__(256, KIN ? 1 : FCG_SWEEP_WGS) void sweep_h8_kernel(
 
     // B. visit stage
     const bool wl = L >= kz0, wl1 = L + 1 < kz1;
-    const uint32_t* recL = sh.prec[ring(L)];
-    const uint32_t* recL1 = sh.prec[ring(L + 1)];
+    constexpr bool kRingSel = !TSI && !DEFER;
+    const int rL = ring(L), rL1 = ring(L + 1);
+    const uint32_t* recL = sh.prec[rL];
+    const uint32_t* recL1 = sh.prec[rL1];
     // linear kinematics: this lane's share of f_A = sum_B K_AB u_B for the row node A of its side
     // (plane L + (k >> 3))
     double fpart[NF];
@@ -754,22 +759,65 @@ __global__ __launch_bounds__(256, KIN ? 1 : FCG_SWEEP_WGS) void sweep_h8_kernel(
       // finished block t of this lane's column (this layer's elements): hold it, or write it plus
       // the part held by lane k + 8 (same role, D side) since the previous layer.  TSI: Tv holds
       // the block's k_ST / k_TS / k_TT entries (tsi_block), treated the same way.
-      auto emit = [&](int act, int t, double* Kb, double* Tv) {
-        // the block's record fields first, all four reads before any branch: one LDS round trip,
-        // which the residual and hold work below overlaps (read one by one behind the early
-        // returns, each waited for in turn)
-        const bool to_l1 = act == kActWriteL1;
-        const uint32_t* rec = to_l1 ? recL1 : recL;
-        const int32_t row0 = WANT_K ? int32_t(rec[PR_ROW0 + c]) : -1;
-        const uint16_t pos = WANT_K ? reinterpret_cast<const uint16_t*>(rec + PR_NPOS)[27 * c + t] : 0;
-        const uint32_t base_lo = WANT_K ? rec[PR_BASE + 2 * c] : 0u;
-        const uint32_t base_hi = WANT_K ? rec[PR_BASE + 2 * c + 1] : 0u;
-        const int32_t len32 = WANT_K ? int32_t(rec[PR_LEN + c]) : 0;
+#ifdef FCG_PROBE_WG3
+      constexpr bool kProbeWg3 = true;
+#else
+      constexpr bool kProbeWg3 = false;
+#endif
+      // An emit in two steps.  emit_load issues every LDS read the block needs -- its record
+      // fields, the neighbour's u and (kBranchFree) the nine held entries -- with no branch between
+      // them: one LDS round trip.  emit_finish does the rest.  The two blocks that end a layer
+      // (the second visit's and the self block) load together ahead of either's work, so that the
+      // pair exposes one round trip, not two (see the end of the visit stage).
+      constexpr bool kBranchFree = !TSI && !DEFER && !kProbeWg3;
+      struct EmitIn {
+        int32_t row0, len32;
+        uint32_t base_lo, base_hi;
+        uint16_t pos;
+        const double* ub;
+        double u0, u1, u2;
+        double* h;
+        double held[9];
+      };
+      auto emit_load = [&](int act, int t, EmitIn& in) {
+        const uint32_t* rec = act == kActWriteL1 ? recL1 : recL;
+        in.row0 = WANT_K ? int32_t(rec[PR_ROW0 + c]) : -1;
+        in.pos = WANT_K ? reinterpret_cast<const uint16_t*>(rec + PR_NPOS)[27 * c + t] : 0;
+        in.base_lo = WANT_K ? rec[PR_BASE + 2 * c] : 0u;
+        in.base_hi = WANT_K ? rec[PR_BASE + 2 * c + 1] : 0u;
+        in.len32 = WANT_K ? int32_t(rec[PR_LEN + c]) : 0;
         if (KIN == 0)
         {
           const int dx = t % 3 - 1, dy = (t / 3) % 3 - 1, dz = t / 9 - 1;
-          const double* ub = &sh.node[ring(L + (k >> 3) + dz)][(cy + 1 + dy) * NXN + cx + 1 + dx][3];
-          const double u0 = ub[0], u1 = ub[1], u2 = ub[2];
+          // the neighbour's plane is L or L + 1 (a layer's elements touch no other): a select
+          // between two uniform ring slots where the registers allow it, not a per-lane % 3
+          const int rU = kRingSel ? (((k >> 3) + dz) ? rL1 : rL) : ring(L + (k >> 3) + dz);
+          in.ub = &sh.node[rU][(cy + 1 + dy) * NXN + cx + 1 + dx][3];
+          in.u0 = in.ub[0];
+          in.u1 = in.ub[1];
+          in.u2 = in.ub[2];
+        }
+        if constexpr (kBranchFree)
+        {
+          // every lane reads nine entries and adds them (emit_finish): the U side its held part,
+          // every other lane the zeros of the spare column (Kb + 0 is Kb but for the sign of a
+          // zero; the D side's sum is not used).  No branch around the reads, no select or copy
+          // behind them.
+          in.h = sh.hold[c][(act == kActHold || act == kActWriteLHold) ? t - 9 : 0];
+          const double* hr = act == kActWriteLHold ? in.h : sh.hold[TX * TY][0];
+#pragma unroll
+          for (int i = 0; i < 9; ++i) in.held[i] = hr[i];
+        }
+      };
+      auto emit_finish = [&](int act, int t, const EmitIn& in, double* Kb, double* Tv) {
+        const bool to_l1 = act == kActWriteL1;
+        const int32_t row0 = in.row0, len32 = in.len32;
+        const uint32_t base_lo = in.base_lo, base_hi = in.base_hi;
+        const uint16_t pos = in.pos;
+        if (KIN == 0)
+        {
+          const double* ub = in.ub;
+          const double u0 = in.u0, u1 = in.u1, u2 = in.u2;
           if (!TH)
 #pragma unroll
             for (int r = 0; r < 3; ++r) fpart[r] += Kb[3 * r] * u0 + Kb[3 * r + 1] * u1 + Kb[3 * r + 2] * u2;
@@ -785,6 +833,19 @@ __global__ __launch_bounds__(256, KIN ? 1 : FCG_SWEEP_WGS) void sweep_h8_kernel(
         }
         // in-plane blocks: every lane of the pair reads the held entry first, then the holder
         // (D side) stores this layer's part and the U side adds the part held since last layer
+        if constexpr (kBranchFree)
+        {
+          // (the caller has put a compiler barrier between the reads and this write: all reads
+          // issue before any write, and the LDS executes a wavefront's operations in order)
+          if (act == kActHold)
+          {
+#pragma unroll
+            for (int i = 0; i < 9; ++i) in.h[i] = Kb[i];
+          }
+#pragma unroll
+          for (int i = 0; i < 9; ++i) Kb[i] = in.held[i] + Kb[i];
+        }
+        else
         if (act == kActHold || act == kActWriteLHold)
         {
           constexpr int NK = TH ? 0 : 9;  // structural entries held (none in the thermal pass)
@@ -952,6 +1013,12 @@ __global__ __launch_bounds__(256, KIN ? 1 : FCG_SWEEP_WGS) void sweep_h8_kernel(
             *d3 += Tv[6];
         }
       };
+      auto emit = [&](int act, int t, double* Kb, double* Tv) {
+        EmitIn in;
+        emit_load(act, t, in);
+        __asm__ volatile("" ::: "memory");
+        emit_finish(act, t, in, Kb, Tv);
+      };
       double acc1[NACC], acc2[NACC];
 #pragma unroll
       for (int i = 0; i < NACC; ++i) acc1[i] = acc2[i] = 0.0;
@@ -973,6 +1040,9 @@ __global__ __launch_bounds__(256, KIN ? 1 : FCG_SWEEP_WGS) void sweep_h8_kernel(
 #define FCG_SWEEP_VISIT_UNROLL (!TSI && KIN == 0)
 #endif
       constexpr int kVisitUnroll = (FCG_SWEEP_VISIT_UNROLL) ? 2 : 1;
+      // unrolled: the second visit's block waits for the self block, and the two load together
+      constexpr bool kPairEmits = kVisitUnroll == 2 && kBranchFree;
+      double Kb2[9];
 #pragma unroll kVisitUnroll
       for (int v = 0; v < 2; ++v)
       {
@@ -991,7 +1061,13 @@ __global__ __launch_bounds__(256, KIN ? 1 : FCG_SWEEP_WGS) void sweep_h8_kernel(
           if (TSI) tsi_block<TH>(A, acc2, Tv);
 #pragma unroll
           for (int i = 0; i < NACC; ++i) acc2[i] = 0.0;
-          emit(int((w >> 21) & 7), int((w >> 16) & 31), Kb, Tv);
+          if (kPairEmits && v == 1)
+          {
+#pragma unroll
+            for (int i = 0; i < 9; ++i) Kb2[i] = Kb[i];
+          }
+          else
+            emit(int((w >> 21) & 7), int((w >> 16) & 31), Kb, Tv);
         }
       }
       // acc1: the self block's two halves meet in lane r = 2 (order: qy = 1 half + qy = 0 half)
@@ -1018,7 +1094,25 @@ __global__ __launch_bounds__(256, KIN ? 1 : FCG_SWEEP_WGS) void sweep_h8_kernel(
             Tv[i] = pair == kPairRecv ? Tv[i] + o : Tv[i];
           }
         }
-        if (pair != kPairGive) emit(int((vis1 >> 21) & 7), int((vis1 >> 11) & 31), Kb, Tv);
+        if constexpr (kPairEmits)
+        {
+          // the reads of both blocks, then (behind a compiler barrier: no hold write may pass a
+          // read; the two blocks' hold slots differ) the second visit's block and the self block
+          const bool fl2 = (vis1 >> 24) & 1u, own = pair != kPairGive;
+          const int act = int((vis1 >> 21) & 7), t2 = int((vis1 >> 16) & 31), t1 = int((vis1 >> 11) & 31);
+          EmitIn in2, in1;
+          // (every lane loads, with no branch: the visit word of a lane without the block still
+          // carries valid fields, the self block's t of its pair lane, so its reads stay in bounds)
+          emit_load(act, t2, in2);
+          emit_load(act, t1, in1);
+          __asm__ volatile("" ::: "memory");
+          if (fl2) emit_finish(act, t2, in2, Kb2, Tv);
+          // (the second block's work stays behind the first's: interleaved, the two cost spills)
+          __builtin_amdgcn_sched_barrier(0);
+          if (own) emit_finish(act, t1, in1, Kb, Tv);
+        }
+        else if (pair != kPairGive)
+          emit(int((vis1 >> 21) & 7), int((vis1 >> 11) & 31), Kb, Tv);
       }
     }
     // residual rows of the column: the 8 lanes of a side sum their parts by a butterfly (every
