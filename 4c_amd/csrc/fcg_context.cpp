@@ -298,6 +298,10 @@ void upload_structured(Uploader& U, const fcg_desc* d, const plan::NodeRows& N, 
   for (int g = 0; g < 8; ++g) tab[384 + g] = w[g];
   for (int k = 0; k < 24; ++k) tab[392 + k] = xi[k];
   U.up(&m.tables, tab);
+  // the checks that depend on the reference coordinates alone, once: a context they pass runs the
+  // sweep without them.  FCG_SWEEP_CHECKED=1 keeps the checked kernels (A/B runs, tests)
+  const char* ck = std::getenv("FCG_SWEEP_CHECKED");
+  if (U.he == hipSuccess) U.chk(fcg::sweep_geometry_pass(m, ck && ck[0] == '1', U.ctx->stream));
 }
 
 void upload_colored(Uploader& U, const fcg_desc* d, const plan::Incidences& I, const plan::ColorHost& cp)
@@ -862,6 +866,9 @@ int fcg_get_diagnostics(const fcg_ctx* ctx, uint64_t* out, int n)
   unsigned long long v[16] = {};
   if (m.stamps && hipMemcpy(v, m.stamps, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess)
     return fcg_device_error();
+  // slot 15 (no kernel counts there): the sweep kernels of this context
+  v[15] = m.path != FCG_PATH_STRUCTURED ? FCG_SWEEP_KERNEL_NA
+                                        : (m.sweep_checked ? FCG_SWEEP_KERNEL_CHECKED : FCG_SWEEP_KERNEL_UNCHECKED);
   for (int i = 0; i < n && i < 16; ++i) out[i] = v[i];
   return m.stamps ? 16 : 0;
 }

@@ -113,6 +113,12 @@ struct DeviceMesh {
   int32_t I0 = 0, J0 = 0, K0 = 0, NI = 0, NJ = 0, NK = 0;  // owned-node lattice box
   int32_t EX0 = 0, EY0 = 0, EZ0 = 0, EX = 0, EY = 0, EZ = 0;  // column-element lattice box
   bool sweep_defer = false;         // rows not in lattice order: sweep MODE 3 (fcg_sweep.hip)
+  // the reference-geometry checks, taken once at create (sweep_geometry_pass): the worst code, the
+  // lowest rejected column element and whether some evaluated element has fac < 0 at a Gauss point.
+  // sweep_checked: the evaluates launch the kernels that repeat these checks (something was found,
+  // or FCG_SWEEP_CHECKED=1); else the CHECKED = false instantiations.
+  int32_t geom_code = 0, geom_ele = INT32_MAX;
+  bool geom_neg = false, sweep_checked = true;
   int32_t* elem_at = nullptr;       // [EZ][EY][EX] column element or -1
   double* lat_x = nullptr;          // [EZ+1][EY+1][EX+1][3] node coordinates on the lattice
   int32_t* lat_dof = nullptr;       // [EZ+1][EY+1][EX+1] column LID of the node's first DOF or -1
@@ -143,6 +149,10 @@ struct DeviceMesh {
 // Launches the structured hex8 row-block sweep (element evaluation + assembly, fcg_sweep.hip).
 hipError_t launch_sweep_h8(const DeviceMesh& m, const double* d_u_col, bool want_k,
     bool overwrite, double* d_K, double* d_fint, hipStream_t stream);
+
+// The sweep's reference-geometry checks, once per context, after lat_x, elem_at and the tile plan
+// are on the device; fills m.geom_* and m.sweep_checked (drains the stream).
+hipError_t sweep_geometry_pass(DeviceMesh& m, bool force_checked, hipStream_t stream);
 
 // Fused TSI blocks of the structured sweep (fcg_tsi_evaluate_fused): linear kinematics, StVK,
 // node-consistent thermo numbering (thermo LID = structural LID / 3, see fcg_tsi.hip).

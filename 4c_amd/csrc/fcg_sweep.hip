@@ -179,7 +179,13 @@ __device__ inline int node_at(int ox, int oy, int oz) { return 4 * oz + (oy ? (o
 
 // Stage A for element slot s, Gauss point g of layer L (element e, -1 = none).  Written for a
 // small register footprint: node data stays in LDS and N_XYZ is recomputed where needed.
-template <int KIN, bool TSI, class SH>
+// The checks that depend on the reference coordinates alone -- det J at node g, det J == 0 at
+// Gauss point g, the sign of fac -- run when CHECKED is set.  GEOM is the create-time geometry
+// pass (sweep_geometry_pass): this same arithmetic up to fac and nothing behind it, the codes
+// into A.err[0..1] as in an evaluate and "some fac < 0" into A.err[2].  A context whose pass found
+// nothing runs CHECKED = false from then on: lat_x does not change during a context's life.
+// A check that reads u (TotLag: F singular) stays in every instantiation.
+template <int KIN, bool TSI, bool CHECKED, bool GEOM, class SH>
 __device__ inline void sweep_stage_a(SH& sh, const SweepArgs& A, int s, int g,
     int sx, int sy, int L, int e)
 {
@@ -189,15 +195,26 @@ __device__ inline void sweep_stage_a(SH& sh, const SweepArgs& A, int s, int g,
 #pragma unroll
   for (int n = 0; n < 8; ++n)
     nd[n] = sh.node[ring(L + node_oz(n))][(sy + node_oy(n)) * NXN + sx + node_ox(n)];
+  // CHECKED: the nodal determinant's reads of the same coordinates, further down, bring all of
+  // them in at once.  Without that block the compiler reads the nodes two by two and waits for
+  // each pair (four exposed LDS round trips per layer): read all eight first, with the Gauss
+  // point's coordinates and weight, in one round trip.
+  double X[8][3];
+#pragma unroll
+  for (int n = 0; n < 8; ++n)
+#pragma unroll
+    for (int d = 0; d < 3; ++d) X[n][d] = nd[n][d];
+  const double gx0 = sh.gxi[g][0], gx1 = sh.gxi[g][1], gx2 = sh.gxi[g][2], wg = sh.w8[g];
+  if constexpr (!CHECKED) __builtin_amdgcn_sched_barrier(0);
   // shape derivatives at Gauss point g from its coordinates (no table loads)
-  const H8dN dn = h8_dn_products(sh.gxi[g][0], sh.gxi[g][1], sh.gxi[g][2]);
+  const H8dN dn = h8_dn_products(gx0, gx1, gx2);
   double J[9];
 #pragma unroll
   for (int q = 0; q < 9; ++q) J[q] = 0.0;
 #pragma unroll
   for (int n = 0; n < 8; ++n)
   {
-    const double x0 = nd[n][0], x1 = nd[n][1], x2 = nd[n][2];
+    const double x0 = X[n][0], x1 = X[n][1], x2 = X[n][2];
     double d0, d1, d2;
     h8_dn(dn, n, d0, d1, d2);
     J[0] += d0 * x0; J[1] += d1 * x0; J[2] += d2 * x0;
@@ -208,6 +225,7 @@ __device__ inline void sweep_stage_a(SH& sh, const SweepArgs& A, int s, int g,
   // det J at node g (calc_lib.hpp:475-496): at a hex8 corner the shape derivatives are
   // +-1/2 on the node and its neighbour along each parametric direction, so J's columns are
   // half the three edge vectors through the node and det J = det(edges) / 8 (same sign).
+  if constexpr (CHECKED)
   {
     const int ox = node_ox(g), oy = node_oy(g), oz = node_oz(g);
     const double* zl = sh.node[ring(L)][0];
@@ -228,10 +246,20 @@ __device__ inline void sweep_stage_a(SH& sh, const SweepArgs& A, int s, int g,
     else if (!(detn > 0)) bad = 1;
   }
   const double det = h8_invert3x3(J);
-  if (det == 0.0) bad = 2;
+  if (CHECKED && det == 0.0) bad = 2;
   // the thermo element's check (4C_thermo_ele_impl.cpp:2663-2664)
   else if (TSI && det < 1e-16 && bad == 0) bad = 1;
-  const double fac = det * sh.w8[g];
+  const double fac = det * wg;
+  if constexpr (GEOM)
+  {
+    if (valid && bad)
+    {
+      atomicMax(&A.err[0], bad);
+      atomicMin(&A.err[1], e);
+    }
+    if (valid && fac < 0.0) atomicMax(&A.err[2], 1);
+    return;
+  }
   // missing element (outside the column set): all its LDS data become exact zeros
   const double sq = valid ? sqrt(fabs(fac)) : 0.0;
   const double cf = fac < 0.0 ? -sq : sq;  // fac / sqrt|fac|
@@ -319,14 +347,19 @@ __device__ inline void sweep_stage_a(SH& sh, const SweepArgs& A, int s, int g,
     t[1] = Tg;
     t[2] = A.tsi_m * cf * trv;
   }
-  if (valid && bad)
+  if constexpr (CHECKED || KIN == 1)
   {
-    atomicMax(&A.err[0], bad);
-    atomicMin(&A.err[1], e);
+    if (valid && bad)
+    {
+      atomicMax(&A.err[0], bad);
+      atomicMin(&A.err[1], e);
+    }
   }
-  const unsigned long long neg = __ballot(valid && fac < 0.0);
-  if (g == 0) sh.neg[s] = uint32_t((neg >> (threadIdx.x & 56)) & 0xFFull);
-
+  if constexpr (CHECKED)
+  {
+    const unsigned long long neg = __ballot(valid && fac < 0.0);
+    if (g == 0) sh.neg[s] = uint32_t((neg >> (threadIdx.x & 56)) & 0xFFull);
+  }
 }
 
 // One element visit: accumulate the blocks (a, b1) into acc1 and (a, b2) into acc2 over the
@@ -558,14 +591,21 @@ __device__ inline void block_k(const StVK& m, const double* acc, double* Kb)
 // 3: structure with the lower-plane blocks deferred one layer (hold_lo), for meshes whose CSR
 // rows do not list the lattice neighbours plane by plane (input-file numbering): a row's 27
 // triples then land all over its 648 bytes, and writing them in two layers' halves left its
-// lines half-written in L2 between the two (1.4x the K bytes written on the renumbered 1M box).
-template <int KIN, bool WANT_K, bool OVERWRITE, int MODE>
+// lines half-written in L2 between the two (1.4x the K bytes written on the renumbered 1M box);
+// 4: the create-time geometry pass (sweep_geometry_pass): the loop's loads of the reference
+// coordinates and the element lattice and stage A's checks, no u, no visit stage, no stores.
+// CHECKED = false (structural passes of a context whose geometry pass found nothing): stage A
+// without the reference-geometry checks, the visit stage without the negative-fac mask and the
+// NEG visit.  The arithmetic that gives nx, gp, K and f is the same: same bits.
+template <int KIN, bool WANT_K, bool OVERWRITE, int MODE, bool CHECKED = true>
 #ifndef FCG_SWEEP_WGS
 #define FCG_SWEEP_WGS 2
 #endif
 __global__ __launch_bounds__(256, KIN ? 1 : FCG_SWEEP_WGS) void sweep_h8_kernel(SweepArgs A)
 {
-  constexpr bool TSI = MODE == 1 || MODE == 2, TH = MODE == 2, DEFER = MODE == 3;
+  constexpr bool TSI = MODE == 1 || MODE == 2, TH = MODE == 2, DEFER = MODE == 3, GEOM = MODE == 4;
+  static_assert(!GEOM || (KIN == 0 && !WANT_K && CHECKED), "the geometry pass is one instantiation");
+  static_assert(CHECKED || !TSI, "the TSI passes keep the checks");
   static_assert(!TSI || (KIN == 0 && WANT_K), "TSI is geometrically linear, full tangent");
   static_assert(!DEFER || WANT_K, "deferred blocks are K blocks");
   __shared__ SweepShared<KIN, TSI, TH, DEFER> sh;
@@ -627,17 +667,21 @@ __global__ __launch_bounds__(256, KIN ? 1 : FCG_SWEEP_WGS) void sweep_h8_kernel(
   auto node_li = [&](int j, int P) -> int64_t { return int64_t(P - A.EZ0) * LX * LY + nlat_xy[j]; };
   auto node_in = [&](int j, int P) -> bool { return nxy_in[j] && P >= A.EZ0 && P <= A.EZ0 + A.EZ; };
   auto load_dof = [&](int j, int P) -> int32_t {
-    if (!node_in(j, P) || ncomp[j] < 3) return -1;
+    if (GEOM || !node_in(j, P) || ncomp[j] < 3) return -1;  // (the geometry pass reads no u)
     return A.lat_dof[node_li(j, P)];
   };
+  // One load instruction behind a selected address, not a load per branch: the lanes of a wave
+  // take different branches, the branches run one after the other, and where the second one's
+  // address arithmetic reused the first one's destination registers the compiler had to wait for
+  // every access in flight (vmcnt(0): the previous layer's K stores) at the top of the layer.
   auto load_val = [&](int j, int P, int32_t dof) -> double {
-    if (!node_in(j, P)) return 0.0;
     const int cp = ncomp[j];
-    if (cp < 3) return A.lat_x[3 * node_li(j, P) + cp];
-    if (dof < 0) return 0.0;
-    if (!TSI || cp < 6) return A.u_col[dof + cp - 3];
-    if (cp < 9) return A.v_col[dof + cp - 6];
-    return A.T_col[dof / 3];
+    const bool has = node_in(j, P) && (cp < 3 || dof >= 0);
+    const double* src = A.lat_x + (3 * node_li(j, P) + cp);
+    if (cp >= 3) src = A.u_col + (dof + cp - 3);
+    if (TSI && cp >= 6) src = A.v_col + (dof + cp - 6);
+    if (TSI && cp >= 9) src = A.T_col + dof / 3;
+    return has ? *src : 0.0;
   };
   auto load_node = [&](int j, int P) -> double { return load_val(j, P, load_dof(j, P)); };
   auto load_rec = [&](int p, uint32_t* w) {
@@ -718,9 +762,9 @@ __global__ __launch_bounds__(256, KIN ? 1 : FCG_SWEEP_WGS) void sweep_h8_kernel(
     // A. element stage
 #ifdef FCG_PROBE_NOSTAGEA
     // timing probe only (wrong results): no element stage
-    if (a_lane && e_cur == -12345) sweep_stage_a<KIN, TSI>(sh, A, s, g, sx, sy, L, e_cur);
+    if (a_lane && e_cur == -12345) sweep_stage_a<KIN, TSI, CHECKED, GEOM>(sh, A, s, g, sx, sy, L, e_cur);
 #else
-    if (a_lane) sweep_stage_a<KIN, TSI>(sh, A, s, g, sx, sy, L, e_cur);
+    if (a_lane) sweep_stage_a<KIN, TSI, CHECKED, GEOM>(sh, A, s, g, sx, sy, L, e_cur);
 #endif
     __syncthreads();
     FCG_STAMP(0);
@@ -732,6 +776,12 @@ __global__ __launch_bounds__(256, KIN ? 1 : FCG_SWEEP_WGS) void sweep_h8_kernel(
       dof_nxt[j] = dof_nn[j];
     }
     store_rec(L + 2, rec_nxt);
+    if constexpr (GEOM)
+    {
+      e_cur = e_nxt;
+      __syncthreads();
+      continue;
+    }
 #ifdef FCG_SWEEP_COMMIT_STAMP
     // diagnostic builds only (it costs the fused TSI pass a spill)
     if (A.stamps)
@@ -1027,7 +1077,7 @@ __global__ __launch_bounds__(256, KIN ? 1 : FCG_SWEEP_WGS) void sweep_h8_kernel(
       // of one ahead of each visit's branch; the TSI instantiation has no registers to spare).
       auto slot_of = [&](uint32_t w) { return (cx + int(w & 1)) + EXN * (cy + int((w >> 1) & 1)); };
       uint32_t nm_pre[2] = {0u, 0u};
-      if constexpr (!TSI)
+      if constexpr (!TSI && CHECKED)
       {
         nm_pre[0] = sh.neg[slot_of(vis0)];
         nm_pre[1] = sh.neg[slot_of(vis1)];
@@ -1049,11 +1099,25 @@ __global__ __launch_bounds__(256, KIN ? 1 : FCG_SWEEP_WGS) void sweep_h8_kernel(
         const uint32_t w = v == 0 ? vis0 : vis1;
         const int a = (w >> 2) & 7, b1 = (w >> 5) & 7, b2 = (w >> 8) & 7;
         const int slot = slot_of(w);
-        const uint32_t nm = TSI ? sh.neg[slot] : (v == 0 ? nm_pre[0] : nm_pre[1]);
-        if (nm == 0u)
-          sweep_visit<KIN, false, TSI, TH>(sh, slot, a, b1, b2, nm, acc1, acc2);
+        if constexpr (!CHECKED)
+        {
+          // An always-taken uniform branch on a value the compiler cannot see through: the visit
+          // keeps a basic block of its own, as under the checked kernel's mask branch.  Inlined
+          // into the surrounding block it costs spills (10-16 VGPRs on the headline kernel, 150
+          // and more on MODE 3 and TotLag); so placed it frees 9 (253 -> 244).  One s_cmp and
+          // one s_cbranch per visit, no LDS read behind it.
+          uint32_t always = 0u;
+          __asm__ volatile("" : "+s"(always));
+          if (always == 0u) sweep_visit<KIN, false, TSI, TH>(sh, slot, a, b1, b2, 0u, acc1, acc2);
+        }
         else
-          sweep_visit<KIN, true, TSI, TH>(sh, slot, a, b1, b2, nm, acc1, acc2);
+        {
+          const uint32_t nm = TSI ? sh.neg[slot] : (v == 0 ? nm_pre[0] : nm_pre[1]);
+          if (nm == 0u)
+            sweep_visit<KIN, false, TSI, TH>(sh, slot, a, b1, b2, nm, acc1, acc2);
+          else
+            sweep_visit<KIN, true, TSI, TH>(sh, slot, a, b1, b2, nm, acc1, acc2);
+        }
         if ((w >> 24) & 1u)
         {
           double Kb[9], Tv[7];
@@ -1233,19 +1297,30 @@ SweepArgs sweep_args(const DeviceMesh& m, const double* d_u_col, double* d_K, do
 }
 }  // namespace
 
-#define FCG_SWEEP(KIN)                                                                             \
+#define FCG_SWEEP_C(KIN, CHECKED)                                                                  \
   if (want_k && m.sweep_defer && overwrite)                                                        \
-    hipLaunchKernelGGL((sweep_h8_kernel<KIN, true, true, 3>), grid, block, 0, stream, a);      \
+    hipLaunchKernelGGL((sweep_h8_kernel<KIN, true, true, 3, CHECKED>), grid, block, 0, stream, a);  \
   else if (want_k && m.sweep_defer)                                                                \
-    hipLaunchKernelGGL((sweep_h8_kernel<KIN, true, false, 3>), grid, block, 0, stream, a);     \
+    hipLaunchKernelGGL((sweep_h8_kernel<KIN, true, false, 3, CHECKED>), grid, block, 0, stream, a); \
   else if (want_k && overwrite)                                                                    \
-    hipLaunchKernelGGL((sweep_h8_kernel<KIN, true, true, 0>), grid, block, 0, stream, a);      \
+    hipLaunchKernelGGL((sweep_h8_kernel<KIN, true, true, 0, CHECKED>), grid, block, 0, stream, a);  \
   else if (want_k)                                                                                 \
-    hipLaunchKernelGGL((sweep_h8_kernel<KIN, true, false, 0>), grid, block, 0, stream, a);     \
+    hipLaunchKernelGGL((sweep_h8_kernel<KIN, true, false, 0, CHECKED>), grid, block, 0, stream, a); \
   else if (overwrite)                                                                              \
-    hipLaunchKernelGGL((sweep_h8_kernel<KIN, false, true, 0>), grid, block, 0, stream, a);     \
+    hipLaunchKernelGGL((sweep_h8_kernel<KIN, false, true, 0, CHECKED>), grid, block, 0, stream, a); \
   else                                                                                             \
-    hipLaunchKernelGGL((sweep_h8_kernel<KIN, false, false, 0>), grid, block, 0, stream, a);
+    hipLaunchKernelGGL((sweep_h8_kernel<KIN, false, false, 0, CHECKED>), grid, block, 0, stream, a);
+// a context whose geometry pass found a code or a negative fac (or FCG_SWEEP_CHECKED=1) keeps the
+// checked kernels: errors and values on every call as the checks give them
+#define FCG_SWEEP(KIN)                                                                             \
+  if (m.sweep_checked)                                                                             \
+  {                                                                                                \
+    FCG_SWEEP_C(KIN, true)                                                                         \
+  }                                                                                                \
+  else                                                                                             \
+  {                                                                                                \
+    FCG_SWEEP_C(KIN, false)                                                                        \
+  }
 
 // The TotLag instantiations live in their own translation unit, fcg_sweep_totlag.hip (this file
 // with FCG_SWEEP_TOTLAG_TU), compiled without the SLP vectorizer: its pairing of the F / S
@@ -1278,6 +1353,46 @@ hipError_t launch_sweep_h8(const DeviceMesh& m, const double* d_u_col, bool want
   const dim3 block{256, 1, 1};
   FCG_SWEEP(0)
   return hipGetLastError();
+}
+
+// The reference-geometry checks of stage A, once per context: the sweep's own kernel (MODE 4) on
+// the sweep's grid, so the elements seen (ghost layers included) and every sign decision are the
+// evaluates'.  Leaves the worst code, the lowest rejected column element and "some evaluated
+// element has fac < 0 at a Gauss point" in m, and picks the kernels the evaluates launch.
+hipError_t sweep_geometry_pass(DeviceMesh& m, bool force_checked, hipStream_t stream)
+{
+  m.geom_code = 0;
+  m.geom_ele = INT32_MAX;
+  m.geom_neg = false;
+  m.sweep_checked = true;
+  const int64_t ntiles = int64_t(m.tiles_x) * m.tiles_y * m.tiles_z;
+  if (ntiles > 0)
+  {
+    int32_t* d_out = nullptr;
+    int32_t out[3] = {0, INT32_MAX, 0};
+    hipError_t he = hipMalloc(reinterpret_cast<void**>(&d_out), sizeof(out));
+    if (he != hipSuccess) return he;
+    he = hipMemcpyAsync(d_out, out, sizeof(out), hipMemcpyHostToDevice, stream);
+    if (he == hipSuccess)
+    {
+      SweepArgs a = sweep_args(m, nullptr, nullptr, nullptr);
+      a.err = d_out;
+      a.stamps = nullptr;
+      const dim3 grid{static_cast<unsigned>(ntiles), 1, 1};
+      const dim3 block{256, 1, 1};
+      hipLaunchKernelGGL((sweep_h8_kernel<0, false, false, 4>), grid, block, 0, stream, a);
+      he = hipGetLastError();
+    }
+    if (he == hipSuccess) he = hipMemcpyAsync(out, d_out, sizeof(out), hipMemcpyDeviceToHost, stream);
+    if (he == hipSuccess) he = hipStreamSynchronize(stream);
+    (void)hipFree(d_out);
+    if (he != hipSuccess) return he;
+    m.geom_code = out[0];
+    m.geom_ele = out[1];
+    m.geom_neg = out[2] != 0;
+  }
+  m.sweep_checked = force_checked || m.geom_code != 0 || m.geom_neg;
+  return hipSuccess;
 }
 
 hipError_t launch_sweep_h8_tsi(const DeviceMesh& m, const double* d_u_col, bool overwrite,
@@ -1322,5 +1437,6 @@ hipError_t launch_sweep_h8_tsi(const DeviceMesh& m, const double* d_u_col, bool 
 }
 #endif  // FCG_SWEEP_TOTLAG_TU
 #undef FCG_SWEEP
+#undef FCG_SWEEP_C
 
 }  // namespace fcg

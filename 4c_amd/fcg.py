@@ -894,6 +894,17 @@ class Evaluator:
         n = lib().fcg_get_diagnostics(self._h, buf, 16)
         return list(buf) if n > 0 else None
 
+    SWEEP_KERNELS = ("not applicable", "checked", "unchecked")
+
+    def sweep_kernel(self):
+        """Which kernels the structured sweep of this context launches (slot 15 of
+        fcg_get_diagnostics): "unchecked" when fcg_create's geometry pass found nothing to reject,
+        "checked" when it did or FCG_SWEEP_CHECKED=1 was set at creation, "not applicable" on
+        the other paths."""
+        buf = (ctypes.c_uint64 * 16)()
+        lib().fcg_get_diagnostics(self._h, buf, 16)
+        return self.SWEEP_KERNELS[int(buf[15])]
+
     CREATE_PHASES = ("checks", "graph_device", "node_rows", "lattice_plans", "incidences",
                      "incidence_positions", "device_plans", "total")
 

@@ -222,7 +222,16 @@ int fcg_measure_hbm(int device, double* copy_gbs, double* write_gbs);
 /* Diagnostics only: with FCG_STAMPS=1 in the environment at fcg_create, the fused kernel sums
  * per-phase cycle counts (s_memtime, thread 0 of every workgroup) into 16 counters: commit,
  * Gauss-point stage, node-row stage, accumulation, flush, workgroups (index 5); the hex27 element
- * kernel's layout is in fcg_hex27.hip.  Returns the number of counters (0 when off). */
+ * kernel's layout is in fcg_hex27.hip.  Returns the number of counters (0 when off).
+ * out[15] is no counter and is filled whether the counters are on or off: which kernels the
+ * structured sweep of this context launches -- FCG_SWEEP_KERNEL_UNCHECKED when the geometry pass
+ * of fcg_create found no rejected element and no negative det J w (the reference coordinates do
+ * not change during a context's life, so the evaluates need not look again),
+ * FCG_SWEEP_KERNEL_CHECKED when it found one or FCG_SWEEP_CHECKED=1 was set at fcg_create,
+ * FCG_SWEEP_KERNEL_NA on every other path. */
+#define FCG_SWEEP_KERNEL_NA 0
+#define FCG_SWEEP_KERNEL_CHECKED 1
+#define FCG_SWEEP_KERNEL_UNCHECKED 2
 int fcg_get_diagnostics(const fcg_ctx* ctx, uint64_t* out, int n);
 
 /* Wall time (seconds) of fcg_create's phases, the setup counterpart of 4C's FillComplete and

@@ -1,5 +1,7 @@
-"""Static issue model of the structured sweep's layer loop (sweep_h8_kernel<0, true, true, 0>, the
-headline kernel): the instructions of one layer per wave from the kernel's ISA, classified by
+"""Static issue model of the structured sweep's layer loop (sweep_h8_kernel<0, true, true, 0, false>,
+the headline kernel: the CHECKED = false instantiation a valid mesh runs; --kernel
+sweep_h8_kernelILi0ELb1ELb1ELi0ELb1E is the checked one, FCG_SWEEP_CHECKED=1 or a mesh the
+create-time geometry pass rejects): the instructions of one layer per wave from the kernel's ISA, classified by
 issue resource and attributed to source lines, against the counters' dynamic counts.
 
 The ISA comes from a device-only compile with line tables, e.g.
@@ -41,7 +43,7 @@ ap.add_argument("pmc", nargs="?")
 ap.add_argument("layers", nargs="?", type=float, default=34.67)
 ap.add_argument("--source", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..",
                                                  "4c_amd", "csrc", "fcg_sweep.hip"))
-ap.add_argument("--kernel", default=r"sweep_h8_kernelILi0ELb1ELb1ELi0E")
+ap.add_argument("--kernel", default=r"sweep_h8_kernelILi0ELb1ELb1ELi0ELb0E")
 ap.add_argument("--lines", type=int, default=24, help="source lines listed")
 args = ap.parse_args()
 
