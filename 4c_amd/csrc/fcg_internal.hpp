@@ -144,6 +144,12 @@ struct DeviceMesh {
   double* mass_tab = nullptr;        // N | dN | w at the Gauss points of the stiffness rule
   double* mass_rho = nullptr;        // [n_ele] per-element densities of the last call that gave them
   int32_t* mass_bad = nullptr;       // [1] lowest column element with det J <= 0 at a Gauss point
+
+  // stress output (fcg_stress.hip), built on the first fcg_gp_stress / fcg_gp_to_nodes
+  double* stress_tab = nullptr;      // dN | w at the Gauss points of the stiffness rule | X^-1
+  double* stress_xinv = nullptr;     // [npe][ngp] inside stress_tab: Gauss points -> nodes
+  int32_t* stress_bad = nullptr;     // [2] lowest column element with det J <= 0 / with det F == 0
+  int32_t* stress_slot = nullptr;    // [n_ele] FCG_PATH_GATHER: ele_mat record of column element e
 };
 
 // Launches the structured hex8 row-block sweep (element evaluation + assembly, fcg_sweep.hip).
@@ -242,6 +248,17 @@ hipError_t launch_mass(const DeviceMesh& m, double density, const double* d_ele_
     bool overwrite, double* d_m_node, double* d_lumped, hipStream_t stream);
 hipError_t launch_effective_tangent(const DeviceMesh& m, double cK, double cM, const double* d_m_node,
     double* d_K, const double* d_x_col, double* d_y_row, hipStream_t stream);
+// Stress output (fcg_stress.hip).  stress_tables_build: the stiffness rule's dN | w table, the
+// Gauss-point-to-node matrix X^-1 and the failing-element words, once per context (drains the
+// stream); stress_slots_build: FCG_PATH_GATHER's inverse of ele_orig for the material table.
+// launch_gp_stress: one lane per (column element, Gauss point), column-element order;
+// launch_gp_to_nodes: one wavefront per column node with an owned row over the mass plan's lists.
+hipError_t stress_tables_build(DeviceMesh& m, int64_t& bytes, hipStream_t stream);
+hipError_t stress_slots_build(DeviceMesh& m, int64_t& bytes, hipStream_t stream);
+hipError_t launch_gp_stress(const DeviceMesh& m, bool cauchy, bool ea, const double* d_u_col,
+    double* d_stress, double* d_strain, double* d_energy, hipStream_t stream);
+hipError_t launch_gp_to_nodes(const DeviceMesh& m, const double* d_gp, double* d_node,
+    hipStream_t stream);
 
 }  // namespace fcg
 

@@ -245,6 +245,13 @@ class GenAlpha:
         return self.d
 
     def energies(self):
-        """(kinetic energy 1/2 v^T M v, None): the internal work is not tracked."""
+        """(kinetic energy 1/2 v^T M v, None): the internal work is not tracked; the strain energy
+        of the current state is internal_energy()."""
         y = self.mass_times(self.v, torch.empty_like(self.v))
         return 0.5 * float(torch.dot(self.v, y)), None
+
+    def internal_energy(self):
+        """The strain energy of the current displacement d: the sum of the elements'
+        sum_g w_g det J_g psi(E_g) (4C's struct_calc_energy through fcg_gp_stress; single rank, so
+        every column element is owned)."""
+        return float(torch.sum(self.ev.strain_energy(self.d)))

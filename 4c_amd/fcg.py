@@ -25,6 +25,8 @@ PATH_AUTO, PATH_GENERAL, PATH_STRUCTURED, PATH_COLORED, PATH_GATHER = 0, 1, 2, 3
 MAT_STVK, MAT_ELASTHYPER_COUPNEOHOOKE = 0, 1
 TSI_STRUCT_FORCE, TSI_STIFFTEMP, TSI_THERMO_FINTCOND, TSI_COUPLTANG = 1, 2, 4, 8
 TSI_ALL = 15
+STRESS_NONE, STRESS_PK2, STRESS_CAUCHY = 0, 1, 2
+STRAIN_NONE, STRAIN_GL, STRAIN_EA = 0, 1, 2
 ABI_VERSION = 2
 
 FCG_OK, FCG_ERR_NODAL_DETJ, FCG_ERR_SINGULAR, FCG_ERR_ARG, FCG_ERR_DEVICE = 0, 1, 2, 3, 4
@@ -154,7 +156,8 @@ EXPORTS = ["fcg_create", "fcg_destroy", "fcg_last_error", "fcg_evaluate", "fcg_e
            "fcg_amg_destroy", "fcg_amg_setup", "fcg_amg_iterate", "fcg_amg_apply",
            "fcg_amg_coupled_levels", "fcg_amg_coupled_stats", "fcg_comm_exchange_device",
            "fcg_transport_rccl", "fcg_dfcg_solve",
-           "fcg_mass_assemble", "fcg_mass_nodal", "fcg_effective_tangent"]
+           "fcg_mass_assemble", "fcg_mass_nodal", "fcg_effective_tangent",
+           "fcg_gp_stress", "fcg_gp_to_nodes"]
 
 _lib = None
 FUNCT_FN = ctypes.CFUNCTYPE(ctypes.c_double, ctypes.c_int, _dp, ctypes.c_double, ctypes.c_void_p)
@@ -318,6 +321,8 @@ def lib():
     L.fcg_mass_assemble.argtypes = [vp, c_dbl, _dp, c_int, vp, vp]
     L.fcg_mass_nodal.argtypes = [vp, c_dbl, _dp, vp, vp, vp]
     L.fcg_effective_tangent.argtypes = [vp, c_dbl, c_dbl, vp, vp, vp, vp, vp]
+    L.fcg_gp_stress.argtypes = [vp, c_int, c_int, vp, vp, vp, vp, vp, _i32p]
+    L.fcg_gp_to_nodes.argtypes = [vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -661,6 +666,7 @@ class Evaluator:
             desc = desc_or_mesh
         self.device = desc.device
         self.kinematics = int(desc.kinematics)
+        self.ngp = 8 if int(desc.celltype) == HEX8 else 27  # the stiffness rule's Gauss points
         h = ctypes.c_void_p()
         rc = L.fcg_create(ctypes.byref(desc), ctypes.byref(h))
         if rc != 0:
@@ -884,6 +890,55 @@ class Evaluator:
                                          self._stream(stream))
         if rc != 0:
             self._raise(rc, -1)
+
+    def gp_stress_raw(self, stress_type, strain_type, u_col, stress=None, strain=None, energy=None,
+                      stream=None):
+        """fcg_gp_stress on the caller's buffers (device tensors or None), unchecked: the C entry
+        point's own argument rules apply.  Waits for the stream."""
+        bad = ctypes.c_int32(-1)
+        rc = lib().fcg_gp_stress(self._h, int(stress_type), int(strain_type), _tensor_ptr(u_col),
+                                 _tensor_ptr(stress), _tensor_ptr(strain), _tensor_ptr(energy),
+                                 self._stream(stream), ctypes.byref(bad))
+        if rc != 0:
+            self._raise(rc, bad.value)
+        lib().fcg_get_info(self._h, ctypes.byref(self.info))  # device_bytes counts the tables
+
+    def gp_stress(self, u_col, stress=STRESS_PK2, strain=STRAIN_GL, energy=False, stream=None):
+        """fcg_gp_stress (4C's struct_calc_stress / struct_calc_energy): the stresses and strains
+        at the Gauss points of every column element, [n_ele, ngp, 6] in Voigt order
+        xx yy zz xy yz xz (strains as tensor components), and with energy=True the elements' strain
+        energies [n_ele].  stress: STRESS_NONE / STRESS_PK2 / STRESS_CAUCHY, strain: STRAIN_NONE /
+        STRAIN_GL / STRAIN_EA.  Returns the tensors asked for, in the order stress, strain, energy
+        (one tensor when only one is asked for).  u_col may be None for linear kinematics."""
+        ngp, n_ele = self.ngp, int(self.info.n_ele)
+        s = self._f64(n_ele * ngp * 6).view(n_ele, ngp, 6) if stress != STRESS_NONE else None
+        e = self._f64(n_ele * ngp * 6).view(n_ele, ngp, 6) if strain != STRAIN_NONE else None
+        w = self._f64(n_ele) if energy else None
+        self.gp_stress_raw(stress, strain, u_col, s, e, w, stream)
+        out = tuple(t for t in (s, e, w) if t is not None)
+        return out[0] if len(out) == 1 else out
+
+    def strain_energy(self, u_col, stream=None):
+        """The elements' strain energies sum_g w_g det J_g psi(E_g), [n_ele] (struct_calc_energy)."""
+        return self.gp_stress(u_col, STRESS_NONE, STRAIN_NONE, True, stream)
+
+    def gp_to_nodes(self, gp, out=None, stream=None):
+        """fcg_gp_to_nodes: Gauss-point data [n_ele, ngp, 6] extrapolated to the element nodes and
+        averaged over each node's elements, [n_node, 6] by column node.  Rows of nodes without an
+        owned row are not written: a fresh `out` is filled with NaN there.  Asynchronous."""
+        import torch
+        ngp = self.ngp
+        if gp.dtype != torch.float64 or gp.numel() != int(self.info.n_ele) * ngp * 6:
+            raise ValueError(f"gp must be float64 [{self.info.n_ele}, {ngp}, 6]")
+        gp = gp.contiguous()
+        if out is None:
+            out = torch.full((int(self.info.n_node), 6), float("nan"), dtype=torch.float64,
+                             device=gp.device)
+        rc = lib().fcg_gp_to_nodes(self._h, _tensor_ptr(gp), _tensor_ptr(out), self._stream(stream))
+        if rc != 0:
+            self._raise(rc, -1)
+        lib().fcg_get_info(self._h, ctypes.byref(self.info))
+        return out
 
     def set_timing(self, enable):
         lib().fcg_set_timing(self._h, 1 if enable else 0)

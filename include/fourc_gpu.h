@@ -301,6 +301,42 @@ int fcg_mass_nodal(fcg_ctx* ctx, double density, const double* ele_density,
 int fcg_effective_tangent(fcg_ctx* ctx, double cK, double cM, const double* d_m_node,
     double* d_K_vals /* may be NULL */, const double* d_x_col, double* d_y_row /* both may be NULL */,
     void* stream);
+/* Output (struct_calc_stress / struct_calc_energy: SolidEleCalc::calculate_stress and
+ * calculate_internal_energy, 4C_solid_3D_ele_calc.cpp): stresses, strains and the strain energy of
+ * every column element at the displacement u_col, in one pass.  Elements in the column-element
+ * order of desc->ele_nodes on every path (ghosts included: the host picks the elements it owns);
+ * Gauss points of the element's stiffness rule (8 / 27, the reference's 13-digit hex27 constants)
+ * in the rule's order; components in 4C's stress Voigt order xx yy zz xy yz xz for stresses and
+ * strains alike, strains in stress-like form (tensor components: eps_xy, not 2 eps_xy).
+ *   FCG_STRAIN_GL  E = 1/2 (F^T F - I); FCG_LINEAR: the symmetric displacement gradient, F := I
+ *   FCG_STRAIN_EA  e = F^-T E F^-1
+ *   FCG_STRESS_PK2 the material's S(E);  FCG_STRESS_CAUCHY  sigma = 1 / det F  F S F^T
+ *   (FCG_LINEAR: EA equals GL and Cauchy equals PK2)
+ *   d_energy[e] = sum_g w_g det J_g psi(E_g) in Gauss-point order; StVK psi = 1/2 E^T C E
+ *   (Mat::StVenantKirchhoff::strain_energy), CoupNeoHooke psi = c (I1 - 3) + c / beta (J^(-2 beta) - 1)
+ * Material: the context's, or the per-element table of fcg_set_element_materials on the paths that
+ * carry one.  d_stress goes with stress_type and d_strain with strain_type: a buffer whose type is
+ * NONE, a type without its buffer, or all three outputs NULL return FCG_ERR_ARG.  d_u_col may be
+ * NULL for FCG_LINEAR (u = 0).  det J <= 0 at a Gauss point returns FCG_ERR_NODAL_DETJ; det F == 0
+ * returns FCG_ERR_SINGULAR where F^-1 or 1 / det F is needed (EA or Cauchy under FCG_TOTLAG); both
+ * report the lowest failing column element through bad_ele_gid and fcg_last_error, through the
+ * solver flag word (never evaluate's sticky flags).  The call returns after the stream has drained.
+ * No atomics on doubles: two calls give the same bits. */
+enum fcg_stress_type { FCG_STRESS_NONE = 0, FCG_STRESS_PK2 = 1, FCG_STRESS_CAUCHY = 2 };
+enum fcg_strain_type { FCG_STRAIN_NONE = 0, FCG_STRAIN_GL = 1, FCG_STRAIN_EA = 2 };
+int fcg_gp_stress(fcg_ctx* ctx, int stress_type, int strain_type, const double* d_u_col,
+    double* d_stress /* [n_ele][ngp][6] or NULL */, double* d_strain /* [n_ele][ngp][6] or NULL */,
+    double* d_energy /* [n_ele] or NULL */, void* stream, int32_t* bad_ele_gid);
+/* The nodal form of Gauss-point data (GAUSS_POINT_DATA_OUTPUT_TYPE nodes:
+ * Core::FE::extrapolate_gauss_points_to_nodes, then the division by the nodal element count): an
+ * element's nodal values are X^-1 gp with X[g][a] = N_a(xi_g) on the stiffness rule (square for
+ * both cell types; inverted once on the host with partial pivoting and kept on the context); every
+ * column node with an owned row gets the mean over all its column elements, summed in ascending
+ * element index (the mass plan's lists, built here if no mass call has).  d_node is indexed by
+ * column node; rows of nodes without an owned row are not touched.  Asynchronous on `stream`
+ * like fcg_spmv. */
+int fcg_gp_to_nodes(fcg_ctx* ctx, const double* d_gp /* [n_ele][ngp][6] */,
+    double* d_node /* [n_node][6] */, void* stream);
 /* K x = b by CG preconditioned with the inverse 3x3 nodal diagonal blocks (block Jacobi) from x = 0 until |r| <= rtol |b| or max_iter iterations;
  * single-rank systems only (matrix column map = row map), else FCG_ERR_ARG.  Deterministic. */
 /* y_row = K x_col with the matrix values stored in FP32 (vectors and sums FP64): the multigrid
