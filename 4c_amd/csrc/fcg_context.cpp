@@ -44,7 +44,7 @@ hipError_t upload(T** dst, const T* src, int64_t n, int64_t& bytes)
 
 void free_mesh(fcg::DeviceMesh& m)
 {
-  void* ptrs[] = {m.node_dof_row, m.node_dof_kcol, m.mass_ptr, m.mass_inc, m.mass_tab, m.mass_rho, m.mass_bad, m.stress_tab, m.stress_bad, m.stress_slot, m.ele_mat, m.apply_ye, m.apply_dof, m.diag_de, m.diag_dbc, m.gather_dummy, m.multi_ptr, m.rec_row0, m.rec_meta, m.rec_base, m.rec_ele, m.rec_a, m.rec_tmap, m.ele_orig, m.inc_ele, m.inc_a, m.asm_order, m.ele_x,
+  void* ptrs[] = {m.node_dof_row, m.node_dof_kcol, m.mass_ptr, m.mass_inc, m.mass_tab, m.mass_rho, m.mass_bad, m.stress_tab, m.stress_bad, m.stress_slot, m.explicit_work, m.ele_mat, m.apply_ye, m.apply_dof, m.diag_de, m.diag_dbc, m.gather_dummy, m.multi_ptr, m.rec_row0, m.rec_meta, m.rec_base, m.rec_ele, m.rec_a, m.rec_tmap, m.ele_orig, m.inc_ele, m.inc_a, m.asm_order, m.ele_x,
       m.ele_dof, m.ele_nodes, m.ele_gid, m.node_x, m.node_dof_col, m.inc_of, m.inc_ptr,
       m.rownode_row0, m.inc_pos, m.rowptr, m.scratch, m.err, m.elem_at, m.lat_x, m.lat_dof,
       m.plane_rec,

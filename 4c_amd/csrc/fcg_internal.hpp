@@ -150,7 +150,13 @@ struct DeviceMesh {
   double* stress_xinv = nullptr;     // [npe][ngp] inside stress_tab: Gauss points -> nodes
   int32_t* stress_bad = nullptr;     // [2] lowest column element with det J <= 0 / with det F == 0
   int32_t* stress_slot = nullptr;    // [n_ele] FCG_PATH_GATHER: ele_mat record of column element e
+
+  // explicit dynamics (fcg_explicit.hip), allocated on the first call that reduces: the
+  // per-workgroup partials of the kinetic energy / the row bound (calls on one context that use
+  // it must be stream-ordered, as with pcg_work), then the bound and the lowest refused row
+  double* explicit_work = nullptr;   // [kExplicitPartials + 2]
 };
+constexpr int kExplicitPartials = 2048;  // the grid cap of the streaming kernels of fcg_explicit.hip
 
 // Launches the structured hex8 row-block sweep (element evaluation + assembly, fcg_sweep.hip).
 hipError_t launch_sweep_h8(const DeviceMesh& m, const double* d_u_col, bool want_k,

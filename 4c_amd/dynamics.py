@@ -255,3 +255,179 @@ class GenAlpha:
         sum_g w_g det J_g psi(E_g) (4C's struct_calc_energy through fcg_gp_stress; single rank, so
         every column element is owned)."""
         return float(torch.sum(self.ev.strain_energy(self.d)))
+
+
+class CentralDifference:
+    """4C's explicit central-difference integrator (DYNAMICTYPE CentrDiff,
+    4C_structure_new_expl_centrdiff.cpp) with the row-sum lumped mass: per step one
+    fcg_evaluate_device (CALC_INTERNALFORCE, OVERWRITE) and one fcg_centrdiff_step, no linear
+    solve.  The update after an evaluate and the one before the next are fused, so the state
+    leapfrogs: after initialize() and n steps
+
+      v, a   = v_n, a_n            at t = t_n
+      vhalf  = v_{n+1/2}
+      d      = d_{n+1}             the displacement the next step evaluates; displacement() gives d_n
+
+    with, per free row (fcg_centrdiff_step; Dirichlet rows keep d and have v = a = 0),
+      a_n = (f_ext(t_n) - f_int(d_n)) / m - damping_m v_{n-1/2}
+      v_n = v_{n-1/2} + dt_{n-1}/2 a_n,  v_{n+1/2} = v_n + dt_n/2 a_n,  d_{n+1} = d_n + dt_n v_{n+1/2}
+    dt may be changed between steps (the attribute `dt` is the next drift's step).  The scheme is
+    stable for dt < 2 / omega_max; stable_dt() returns a step that is never above that limit.
+
+    Single rank, homogeneous-in-time Dirichlet conditions; d, vhalf, v, a, f_int and the kinetic
+    energy stay in HBM, t and nstep are host numbers (they need no device work).  All launches go
+    to torch's current stream of the evaluator's device."""
+
+    def __init__(self, evaluator, density, dt, fext, dbc_rows, damping_m=0.0, ele_density=None):
+        """fext: a row vector (constant load) or a callable t -> row vector (numpy or device
+        tensor).  damping_m: mass-proportional damping C = damping_m M, taken at the half-step
+        velocity.  density / ele_density: as Evaluator.mass_nodal."""
+        info = evaluator.info
+        self.ev = evaluator
+        self.dev = torch.device("cuda", evaluator.device)
+        self.n = int(info.n_rows)
+        if int(info.n_cols) != self.n:
+            raise ValueError("CentralDifference is single-rank: the column map must be the row map")
+        self.nnz = int(info.nnz)
+        self.dt = float(dt)
+        if not self.dt > 0.0:
+            raise ValueError("dt must be positive")
+        self.damp_m = float(damping_m)
+        if not self.damp_m >= 0.0:
+            raise ValueError("damping_m must not be negative")
+        f64 = dict(dtype=torch.float64, device=self.dev)
+        self.m_lumped = torch.empty(self.n, **f64)
+        evaluator.mass_nodal(density, ele_density, None, self.m_lumped)
+        if self.n and not float(self.m_lumped.min()) > 0.0:
+            raise ValueError("the lumped mass is not positive on every row")
+        dbc = np.unique(np.asarray(dbc_rows, dtype=np.int64))
+        if len(dbc) and (dbc[0] < 0 or dbc[-1] >= self.n):
+            raise ValueError("a Dirichlet row lies outside the row map")
+        fixed = np.zeros(self.n, dtype=np.uint8)
+        fixed[dbc] = 1
+        self.fixed = torch.as_tensor(fixed).to(self.dev)
+        self._fext = fext
+        self._fext_const = None if callable(fext) else self._as_row(fext).clone()
+        self.d = torch.zeros(self.n, **f64)
+        self.vhalf = torch.zeros(self.n, **f64)
+        self.v = torch.zeros(self.n, **f64)
+        self.a = torch.zeros(self.n, **f64)
+        self.fint = torch.zeros(self.n, **f64)
+        self.ekin = torch.zeros(1, **f64)
+        self.t = 0.0
+        self.nstep = 0
+        self._dt_last = 0.0  # the step of the drift that produced d
+        self._initialized = False
+
+    # ------------------------------------------------------------------ pieces
+    def _as_row(self, f):
+        if not torch.is_tensor(f):
+            f = torch.as_tensor(np.asarray(f, dtype=np.float64))
+        f = f.to(device=self.dev, dtype=torch.float64)
+        if f.numel() != self.n:
+            raise ValueError(f"fext has {f.numel()} entries, the context {self.n} rows")
+        return f
+
+    def fext_at(self, t):
+        return self._fext_const if self._fext_const is not None else self._as_row(self._fext(t))
+
+    def _advance(self, t_eval, dt_prev):
+        """f_int(d), then the fused update with f_ext(t_eval): d is the displacement at t_eval."""
+        fext = self.fext_at(t_eval)
+        self.ev.evaluate_device(fcg.CALC_INTERNALFORCE, fcg.OVERWRITE, self.d, self.fint)
+        self.ev.centrdiff_step(dt_prev, self.dt, self.damp_m, fext, self.fint, self.m_lumped,
+                               self.fixed, self.d, self.vhalf, self.v, self.a, self.ekin)
+        self._dt_last = self.dt
+
+    # ------------------------------------------------------------------ the integration
+    def initialize(self, u0=None, v0=None):
+        """Sets d_0 and v_0, forms a_0 = (f_ext(0) - f_int(d_0)) / m - damping_m v_0 and takes the
+        first half kick and drift (dt_prev = 0).  Returns a_0."""
+        f64 = dict(dtype=torch.float64, device=self.dev)
+        self.d = (torch.zeros(self.n, **f64) if u0 is None
+                  else torch.as_tensor(u0, dtype=torch.float64).to(self.dev).clone())
+        self.vhalf = (torch.zeros(self.n, **f64) if v0 is None
+                      else torch.as_tensor(v0, dtype=torch.float64).to(self.dev).clone())
+        self.t, self.nstep = 0.0, 0
+        self._advance(0.0, 0.0)
+        self._initialized = True
+        return self.a
+
+    def step(self):
+        """One evaluate at d_{n+1} and one fused update: (v, a, t) advance to t_{n+1}, d to
+        d_{n+2}.  Returns d."""
+        if not self._initialized:
+            self.initialize()
+        t_new = self.t + self._dt_last
+        self._advance(t_new, self._dt_last)
+        self.t = t_new
+        self.nstep += 1
+        return self.d
+
+    def run(self, n_steps, check_every=100):
+        """n_steps steps.  With a constant fext the evaluator is switched to set_async(1) and the
+        steps are queued without any host synchronisation; check_error() runs every check_every
+        steps and at the end, and an element error (4C's throws) surfaces as FcgError with the
+        step range in which it happened -- the state tensors are then not usable.  A callable fext
+        is evaluated on the host per step, in the evaluator's own mode.  The evaluator's async
+        setting is restored on every exit path.  Returns d."""
+        check_every = max(1, int(check_every))
+        prev = self.ev.async_enabled
+        failed = False
+        try:
+            if self._fext_const is not None:
+                self.ev.set_async(1)
+            lo = self.nstep + 1
+            try:
+                if not self._initialized:
+                    lo = 0  # step 0: the evaluate of initialize()
+                    self.initialize()
+                for k in range(int(n_steps)):
+                    self.step()
+                    if (k + 1) % check_every == 0:
+                        self.ev.check_error()
+                        lo = self.nstep + 1
+                self.ev.check_error()
+            except fcg.FcgError as e:
+                msg = str(e).split(": ", 1)[-1]
+                raise fcg.FcgError(e.code, f"CentralDifference.run, steps {lo}..{max(lo, self.nstep)}: "
+                                   f"{msg}", e.bad_ele_gid) from e
+        except BaseException:
+            failed = True
+            raise
+        finally:
+            try:
+                self.ev.set_async(prev)
+            except fcg.FcgError:
+                # leaving async mode reports what was still pending; the context is synchronous now
+                if prev:
+                    self.ev.set_async(1)
+                if not failed:
+                    raise
+        return self.d
+
+    # ------------------------------------------------------------------ output
+    def displacement(self):
+        """d_n, the displacement at the time t of v and a: d - dt vhalf (a new tensor)."""
+        return torch.add(self.d, self.vhalf, alpha=-self._dt_last)
+
+    def energies(self):
+        """(kinetic energy 1/2 v^T M v at t, None), the kinetic part from fcg_centrdiff_step's
+        fixed-order sum; the strain energy is internal_energy()."""
+        return float(self.ekin), None
+
+    def internal_energy(self):
+        """The strain energy of displacement(): the sum of the elements' sum_g w_g det J_g psi(E_g)
+        (fcg_gp_stress; single rank, so every column element is owned)."""
+        return float(torch.sum(self.ev.strain_energy(self.displacement())))
+
+    def stable_dt(self, safety=1.0):
+        """safety x the Gershgorin bound 2 / sqrt(max_i sum_j |K_ij| / m_i) of fcg_stable_dt on the
+        free rows, with K assembled at the current d into a buffer that lives only for this call.
+        Never above the central-difference limit 2 / omega_max of K(d)."""
+        f64 = dict(dtype=torch.float64, device=self.dev)
+        K = torch.empty(self.nnz, **f64)
+        f = torch.empty(self.n, **f64)
+        self.ev.evaluate_device(fcg.CALC_NLNSTIFF, fcg.OVERWRITE, self.d, f, K)
+        dt_crit, _ = self.ev.stable_dt(K, self.m_lumped, self.fixed)
+        return float(safety) * dt_crit

@@ -157,7 +157,8 @@ EXPORTS = ["fcg_create", "fcg_destroy", "fcg_last_error", "fcg_evaluate", "fcg_e
            "fcg_amg_coupled_levels", "fcg_amg_coupled_stats", "fcg_comm_exchange_device",
            "fcg_transport_rccl", "fcg_dfcg_solve",
            "fcg_mass_assemble", "fcg_mass_nodal", "fcg_effective_tangent",
-           "fcg_gp_stress", "fcg_gp_to_nodes"]
+           "fcg_gp_stress", "fcg_gp_to_nodes",
+           "fcg_centrdiff_step", "fcg_stable_dt"]
 
 _lib = None
 FUNCT_FN = ctypes.CFUNCTYPE(ctypes.c_double, ctypes.c_int, _dp, ctypes.c_double, ctypes.c_void_p)
@@ -323,6 +324,8 @@ def lib():
     L.fcg_effective_tangent.argtypes = [vp, c_dbl, c_dbl, vp, vp, vp, vp, vp]
     L.fcg_gp_stress.argtypes = [vp, c_int, c_int, vp, vp, vp, vp, vp, _i32p]
     L.fcg_gp_to_nodes.argtypes = [vp, vp, vp, vp]
+    L.fcg_centrdiff_step.argtypes = [vp, c_dbl, c_dbl, c_dbl, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.fcg_stable_dt.argtypes = [vp, vp, vp, vp, _dp, _dp, vp]
     _lib = L
     return L
 
@@ -676,6 +679,7 @@ class Evaluator:
         L.fcg_get_info(h, ctypes.byref(info))
         self.info = info
         self._n_materials = 0
+        self._async = False
 
     @property
     def n_materials(self):
@@ -762,8 +766,14 @@ class Evaluator:
     def set_async(self, enable):
         """fcg_set_async: evaluate_device returns once queued; check_error reports failures."""
         rc = lib().fcg_set_async(self._h, 1 if enable else 0)
+        self._async = bool(enable) and rc == 0  # a failed call leaves the context synchronous
         if rc != 0:
             self._raise(rc, -1)
+
+    @property
+    def async_enabled(self):
+        """The setting of the last set_async (contexts start synchronous)."""
+        return self._async
 
     def check_error(self):
         bad = ctypes.c_int32(-1)
@@ -939,6 +949,36 @@ class Evaluator:
             self._raise(rc, -1)
         lib().fcg_get_info(self._h, ctypes.byref(self.info))
         return out
+
+    def centrdiff_step(self, dt_prev, dt_next, damp_m, fext, fint, m_lumped, fixed, d, vhalf,
+                       v=None, a=None, ekin=None, stream=None):
+        """fcg_centrdiff_step: one central-difference update over the owned rows.  On entry d =
+        d_{n+1}, vhalf = v_{n+1/2}, fint = f_int(d), fext = f_ext(t_{n+1}); d and vhalf advance in
+        place to d_{n+2} and v_{n+3/2}, v and a (optional) receive v_{n+1} and a_{n+1}, ekin (one
+        double, optional) 1/2 sum m v^2.  fixed: uint8 device tensor, != 0 marks a Dirichlet row,
+        or None.  All float64 device tensors [n_rows].  Asynchronous."""
+        rc = lib().fcg_centrdiff_step(self._h, float(dt_prev), float(dt_next), float(damp_m),
+                                      _tensor_ptr(fext), _tensor_ptr(fint), _tensor_ptr(m_lumped),
+                                      _tensor_ptr(fixed), _tensor_ptr(d), _tensor_ptr(vhalf),
+                                      _tensor_ptr(v), _tensor_ptr(a), _tensor_ptr(ekin),
+                                      self._stream(stream))
+        if rc != 0:
+            self._raise(rc, -1)
+        if ekin is not None:
+            lib().fcg_get_info(self._h, ctypes.byref(self.info))  # device_bytes counts the partials
+
+    def stable_dt(self, K_vals, m_lumped, fixed=None, stream=None):
+        """fcg_stable_dt: (dt_crit, lambda_bound) with lambda_bound = max over the free rows of
+        sum_j |K_ij| / m_i (Gershgorin) and dt_crit = 2 / sqrt(lambda_bound), never above the
+        central-difference limit 2 / omega_max.  This rank's rows only.  Waits for the stream."""
+        lam, dt = ctypes.c_double(0.0), ctypes.c_double(0.0)
+        rc = lib().fcg_stable_dt(self._h, _tensor_ptr(K_vals), _tensor_ptr(m_lumped),
+                                 _tensor_ptr(fixed), ctypes.byref(lam), ctypes.byref(dt),
+                                 self._stream(stream))
+        if rc != 0:
+            self._raise(rc, -1)
+        lib().fcg_get_info(self._h, ctypes.byref(self.info))
+        return dt.value, lam.value
 
     def set_timing(self, enable):
         lib().fcg_set_timing(self._h, 1 if enable else 0)
