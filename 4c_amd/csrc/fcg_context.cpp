@@ -915,8 +915,8 @@ int fcg_set_element_materials(fcg_ctx* ctx, int32_t n_mat, const double* youngs,
   {
     if (m.path == FCG_PATH_STRUCTURED || m.path == FCG_PATH_COLORED)
       return refuse(std::string("the ") + (m.path == FCG_PATH_STRUCTURED ? "structured sweep" : "coloured lattice assembly") +
-                    " takes one material per context; create the context with FCG_PATH_GATHER (hex8 "
-                    "St.Venant-Kirchhoff) or FCG_PATH_GENERAL");
+                    " takes one material per context; create the context with FCG_PATH_GATHER (hex8) "
+                    "or FCG_PATH_GENERAL");
     if (!youngs || !poisson || (m.n_ele > 0 && !ele_mat))
       return refuse("n_mat > 0 needs youngs, poisson and ele_mat (one of them is NULL)");
     // Mat::PAR::StVenantKirchhoff parameter checks, as fcg_create's

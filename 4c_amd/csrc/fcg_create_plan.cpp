@@ -818,7 +818,8 @@ int check_descriptor(const fcg_desc* d, std::string& why)
   if (d->material == FCG_MAT_ELASTHYPER_COUPNEOHOOKE && d->kinematics != FCG_TOTLAG)
     return refuse(why, "ElastHyper is supported with KINEM nonlinear (TotLag) only");
   if (d->material != FCG_MAT_STVK && d->path == FCG_PATH_STRUCTURED && d->celltype == FCG_HEX8)
-    return refuse(why, "the structured sweep implements StVenantKirchhoff only");
+    return refuse(why, "the structured sweep implements StVenantKirchhoff only (hex8 "
+                       "ElastHyper/CoupNeoHooke: FCG_PATH_GATHER or FCG_PATH_GENERAL)");
   // rowptr = col_lid = NULL: the graph is built on the device (FillComplete of the first
   // assembly); one of the two alone is an error
   const bool build_graph = d->n_rows > 0 && !d->rowptr && !d->col_lid;
@@ -953,11 +954,13 @@ int choose_path(const fcg_desc* d, const NodeRows& N, int cus, PathChoice& P, st
   }
   if (d->path == FCG_PATH_COLORED && d->celltype != FCG_HEX27)
     return refuse(why, "the colour-ordered path is implemented for hex27");
-  // --- node-row gather: hex8 StVK meshes without a verified lattice (AUTO), or on request
-  if (d->path == FCG_PATH_GATHER && (d->celltype != FCG_HEX8 || d->material != FCG_MAT_STVK))
-    return refuse(why, "the gather path is implemented for hex8 with StVenantKirchhoff");
-  P.gather = !P.structured && d->celltype == FCG_HEX8 && d->material == FCG_MAT_STVK &&
-             (d->path == FCG_PATH_GATHER || d->path == FCG_PATH_AUTO);
+  // --- node-row gather: hex8 StVK meshes without a verified lattice (AUTO), or on request (StVK
+  // and ElastHyper/CoupNeoHooke; AUTO keeps CoupNeoHooke on the general path)
+  if (d->path == FCG_PATH_GATHER && d->celltype != FCG_HEX8)
+    return refuse(why, "the gather path is implemented for hex8 (StVenantKirchhoff and "
+                       "ElastHyper/CoupNeoHooke)");
+  P.gather = !P.structured && d->celltype == FCG_HEX8 &&
+             (d->path == FCG_PATH_GATHER || (d->path == FCG_PATH_AUTO && d->material == FCG_MAT_STVK));
   return FCG_OK;
 }
 

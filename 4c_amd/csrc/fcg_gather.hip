@@ -12,11 +12,14 @@
 //      det J > 0 check at corner g (calc_lib.hpp:475-496, same coefficients at xi = +-1), N_XYZ of
 //      the 8 nodes; TotLag also F (hex8: from current coordinates, calc_lib.hpp:579-595, here as
 //      J_cur J^-1), E, StVK S (4C_mat_stvenantkirchhoff.cpp:169-177) and the Gauss point's part of
-//      f_A = sum_g fac F S N_XYZ_A (calc_lib.hpp:851-860);
+//      f_A = sum_g fac F S N_XYZ_A (calc_lib.hpp:851-860); ElastHyper/CoupNeoHooke (TotLag) instead
+//      J_cur^-1, p = (det F)^(-2 beta) and its f_A part (see gather_h8_kernel);
 //   3. lane (j, b): the 3 x 3 block K_ab of A's local node a with element node b over the Gauss
 //      points,
 //        linear  K_ab = sum_g fac [lambda a b^T + mu b a^T + mu (a.b) I]
 //        TotLag  K_ab = sum_g fac [lambda (Fa)(Fb)^T + mu (Fb)(Fa)^T + mu (a.b) F F^T + (a.S.b) I]
+//        CoupNeoHooke  K_ab = sum_g fac [lambda0 p alpha beta_b^T + mu0 p beta_b alpha^T + mu0 (a.b) I],
+//                      alpha = F^-T a, beta_b = F^-T b
 //      (= B_a^T C B_b + K_geo of calc_lib.hpp:872-927 for the isotropic C of fill_cmat); linear
 //      f_A part K_ab u_b (f_int = K u exactly);
 //   4. the 64 blocks are summed per target entry of A's three CSR rows: lane v takes row entries
@@ -65,6 +68,7 @@ struct GatherShared {
   static constexpr int kGp = KIN ? 25 : 3;  // A/B probe: the round-5 strides (ds_read2_b64 pairs)
   static constexpr int kGpSlot = KIN ? 200 : 24;
 #else
+  // (CoupNeoHooke fills the first 15 of the 26: fac p alpha, J^-T fac a, F^-T J^-T)
   static constexpr int kGp = KIN ? 26 : 3;  // per (slot, GP): fac a | TotLag: fac F a, J^-T fac S a, F J^-T, F F^T, J^-T fac a
   static constexpr int kGpSlot = KIN ? 216 : 24;
 #endif
@@ -116,7 +120,10 @@ struct GatherArgs {
   int32_t* err;
   double* dummy;             // [3] target of the stores of a row without columns
   StVK mat;
-  const double* ele_mat;     // [n_ele][4] TAB: lambda, mu, cdiag, 0 of each storage slot's element
+  double nh_c, nh_beta;      // ElastHyper/CoupNeoHooke: c = E / (4 (1 + nu)), beta = nu / (1 - 2 nu)
+  // [n_ele][4] TAB: lambda, mu, cdiag, 0 (StVK) or c, beta, 0, 0 (CoupNeoHooke) of each storage
+  // slot's element
+  const double* ele_mat;
 };
 
 // hex8 corner n in 4C order: parametric coordinate signs
@@ -182,9 +189,21 @@ __device__ inline double wave_sum(double v)
 // TAB: per-element material constants (A.ele_mat) instead of the uniform A.mat -- a lane works on
 // its slot's element throughout, so it carries that element's constants: the stress of stage 2 and
 // the block combination of stage 3 then hold per slot, before the row sum of stage 4
-template <int KIN, bool WANT_K, bool OVERWRITE, bool MULTI, bool TAB = false>
+//
+// MAT = FCG_MAT_ELASTHYPER_COUPNEOHOOKE (TotLag only).  With p = I3^-beta, I3 = det C, the material
+// gives S = 2c (I - p C^-1) and cmat = 4 c beta p C^-1 (x) C^-1 + 4 c p C^-1 odot C^-1
+// (neohooke_stress_cmat of fcg_kernels.hip).  With alpha = F^-T a, beta_b = F^-T b (F C^-1 = F^-T,
+// F C^-1 F^T = I) the (alpha . beta_b) I terms of B_a^T cmat B_b and of K_geo cancel, and
+//   K_ab = lambda0 G + mu0 G^T + mu0 (sum_g fac a.b) I,   G = sum_g (fac p alpha) beta_b^T,
+//   f_A  = sum_g fac 2c (F a - p alpha),                  lambda0 = 4 c beta, mu0 = 2 c:
+// StVK's stage 3 with F^-T in the place of F, p folded into the Gauss point's factor and no F F^T
+// sum.  The record of a (slot, Gauss point) holds fac p alpha | J^-T-folded fac a | F^-T J^-T in
+// doubles [0, 15) of the StVK record's 26, so the LDS layout is the same.
+template <int KIN, bool WANT_K, bool OVERWRITE, bool MULTI, bool TAB = false, int MAT = FCG_MAT_STVK>
 __global__ __launch_bounds__(64, 2) void gather_h8_kernel(GatherArgs A)
 {
+  constexpr bool NH = MAT == FCG_MAT_ELASTHYPER_COUPNEOHOOKE;
+  static_assert(!NH || KIN == 1, "ElastHyper/CoupNeoHooke takes TotLag kinematics");
   using Sh = GatherShared<KIN, MULTI>;
   __shared__ Sh sh;
   const int lane = threadIdx.x;
@@ -266,7 +285,7 @@ __global__ __launch_bounds__(64, 2) void gather_h8_kernel(GatherArgs A)
       const double2 v = p[0], w = p[1];
       mv[0] = v.x;
       mv[1] = v.y;
-      mv[2] = w.x;
+      mv[2] = w.x;  // (CoupNeoHooke uses c, beta only)
     }
   };
   auto load_u = [&](int32_t dof, double* u) {
@@ -380,6 +399,7 @@ __global__ __launch_bounds__(64, 2) void gather_h8_kernel(GatherArgs A)
       const double pxz[2][2] = {{hxm * zm, hxm * zp}, {hxp * zm, hxp * zp}};
       const double pxy[2][2] = {{hxm * ym, hxm * yp}, {hxp * ym, hxp * yp}};
       double na[3];
+      double da[3] = {0.0, 0.0, 0.0};  // dN_a / dxi at the Gauss point (CoupNeoHooke)
       if (KIN == 0)
       {
 #pragma unroll
@@ -411,6 +431,9 @@ __global__ __launch_bounds__(64, 2) void gather_h8_kernel(GatherArgs A)
         na[0] = J[0] * d0 + J[3] * d1 + J[6] * d2;
         na[1] = J[1] * d0 + J[4] * d1 + J[7] * d2;
         na[2] = J[2] * d0 + J[5] * d1 + J[8] * d2;
+        da[0] = d0;
+        da[1] = d1;
+        da[2] = d2;
       }
       double* P = sh.GP(j, q);
       if (KIN == 0)
@@ -430,48 +453,93 @@ __global__ __launch_bounds__(64, 2) void gather_h8_kernel(GatherArgs A)
           for (int jj = 0; jj < 3; ++jj)
             F[ii + 3 * jj] = Jc[0 + 3 * ii] * J[jj + 0] + Jc[1 + 3 * ii] * J[jj + 3] + Jc[2 + 3 * ii] * J[jj + 6];
         if (h8_det(F) == 0.0) bad = 2;
-        const double C0 = F[0] * F[0] + F[1] * F[1] + F[2] * F[2];
-        const double C4 = F[3] * F[3] + F[4] * F[4] + F[5] * F[5];
-        const double C8 = F[6] * F[6] + F[7] * F[7] + F[8] * F[8];
-        const double C3 = F[0] * F[3] + F[1] * F[4] + F[2] * F[5];
-        const double C7 = F[3] * F[6] + F[4] * F[7] + F[5] * F[8];
-        const double C2 = F[6] * F[0] + F[7] * F[1] + F[8] * F[2];
-        const double E0 = 0.5 * (C0 - 1.0), E1 = 0.5 * (C4 - 1.0), E2 = 0.5 * (C8 - 1.0);
-        StVK m = A.mat;
-        if constexpr (TAB) m = StVK{mc[0], mc[1], mc[2]};
-        const double S0 = m.cdiag * E0 + m.lambda * E1 + m.lambda * E2;
-        const double S1 = m.lambda * E0 + m.cdiag * E1 + m.lambda * E2;
-        const double S2 = m.lambda * E0 + m.lambda * E1 + m.cdiag * E2;
-        const double S3 = m.mu * C3, S4 = m.mu * C7, S5 = m.mu * C2;
-        const double sa0 = S0 * na[0] + S3 * na[1] + S5 * na[2];
-        const double sa1 = S3 * na[0] + S1 * na[1] + S4 * na[2];
-        const double sa2 = S5 * na[0] + S4 * na[1] + S2 * na[2];
-        // f_A part: fac F S N_XYZ_A
-        fp0 = fac * (F[0] * sa0 + F[3] * sa1 + F[6] * sa2);
-        fp1 = fac * (F[1] * sa0 + F[4] * sa1 + F[7] * sa2);
-        fp2 = fac * (F[2] * sa0 + F[5] * sa1 + F[8] * sa2);
-        // stage 3 needs, for N_XYZ_b = J^-T dN_b (b_j = sum_dir J[j + 3 dir] d_dir):
-        //   fac F a | J^-T-folded fac S a | Q = F J^-T (Q[i + 3 dir]) | F F^T | J^-T-folded fac a
-        const double fs0 = fac * sa0, fs1 = fac * sa1, fs2 = fac * sa2;
-        const double fa0 = fac * na[0], fa1 = fac * na[1], fa2 = fac * na[2];
-        P[0] = F[0] * fa0 + F[3] * fa1 + F[6] * fa2;
-        P[1] = F[1] * fa0 + F[4] * fa1 + F[7] * fa2;
-        P[2] = F[2] * fa0 + F[5] * fa1 + F[8] * fa2;
-#pragma unroll
-        for (int dir = 0; dir < 3; ++dir)
+        if constexpr (NH)
         {
-          const double j0 = J[0 + 3 * dir], j1 = J[1 + 3 * dir], j2 = J[2 + 3 * dir];
-          P[3 + dir] = fs0 * j0 + fs1 * j1 + fs2 * j2;
-          P[21 + dir] = fa0 * j0 + fa1 * j1 + fa2 * j2;
+          const double detF = h8_det(F);
+          const double Fa0 = F[0] * na[0] + F[3] * na[1] + F[6] * na[2];
+          const double Fa1 = F[1] * na[0] + F[4] * na[1] + F[7] * na[2];
+          const double Fa2 = F[2] * na[0] + F[5] * na[1] + F[8] * na[2];
+          // F^-T J^-T = J_cur^-T: F^-T N_XYZ_b is the spatial gradient of N_b, formed from the
+          // current Jacobian's inverse W[i + 3 dir] = d xi_dir / d x_i (a singular J_cur: code 2,
+          // like det F = 0)
+          if (h8_invert3x3(Jc) == 0.0) bad = 2;
+          // alpha = F^-T a = W dN_a; f_A part: fac 2c (F a - p alpha)
+          const double al0 = Jc[0] * da[0] + Jc[3] * da[1] + Jc[6] * da[2];
+          const double al1 = Jc[1] * da[0] + Jc[4] * da[1] + Jc[7] * da[2];
+          const double al2 = Jc[2] * da[0] + Jc[5] * da[1] + Jc[8] * da[2];
+          // stage 3 needs, for N_XYZ_b = J^-T dN_b: fac p alpha | J^-T-folded fac a |
+          // Q = F^-T J^-T (Q[i + 3 dir])
+          if (WANT_K)
+          {
+            const double fa0 = fac * na[0], fa1 = fac * na[1], fa2 = fac * na[2];
 #pragma unroll
-          for (int ii = 0; ii < 3; ++ii) P[6 + ii + 3 * dir] = F[ii] * j0 + F[ii + 3] * j1 + F[ii + 6] * j2;
+            for (int dir = 0; dir < 3; ++dir)
+              P[3 + dir] = fa0 * J[0 + 3 * dir] + fa1 * J[1 + 3 * dir] + fa2 * J[2 + 3 * dir];
+#pragma unroll
+            for (int k = 0; k < 9; ++k) P[6 + k] = Jc[k];
+          }
+          // I3 = det C = (det F)^2, p = I3^-beta; I3 <= 0: NaN, as neohooke_stress_cmat (last: the
+          // matrices above are no longer live across the exp and log)
+          const double I3 = detF * detF;
+          const double nc = TAB ? mc[0] : A.nh_c, nbeta = TAB ? mc[1] : A.nh_beta;
+          const double p = I3 > 0 ? exp(log(I3) * -nbeta) : NAN;
+          const double f2c = fac * (2.0 * nc);
+          fp0 = f2c * (Fa0 - p * al0);
+          fp1 = f2c * (Fa1 - p * al1);
+          fp2 = f2c * (Fa2 - p * al2);
+          if (WANT_K)
+          {
+            const double fpp = fac * p;
+            P[0] = fpp * al0;
+            P[1] = fpp * al1;
+            P[2] = fpp * al2;
+          }
         }
-        P[15] = F[0] * F[0] + F[3] * F[3] + F[6] * F[6];
-        P[16] = F[1] * F[1] + F[4] * F[4] + F[7] * F[7];
-        P[17] = F[2] * F[2] + F[5] * F[5] + F[8] * F[8];
-        P[18] = F[0] * F[1] + F[3] * F[4] + F[6] * F[7];
-        P[19] = F[1] * F[2] + F[4] * F[5] + F[7] * F[8];
-        P[20] = F[2] * F[0] + F[5] * F[3] + F[8] * F[6];
+        else
+        {
+          const double C0 = F[0] * F[0] + F[1] * F[1] + F[2] * F[2];
+          const double C4 = F[3] * F[3] + F[4] * F[4] + F[5] * F[5];
+          const double C8 = F[6] * F[6] + F[7] * F[7] + F[8] * F[8];
+          const double C3 = F[0] * F[3] + F[1] * F[4] + F[2] * F[5];
+          const double C7 = F[3] * F[6] + F[4] * F[7] + F[5] * F[8];
+          const double C2 = F[6] * F[0] + F[7] * F[1] + F[8] * F[2];
+          const double E0 = 0.5 * (C0 - 1.0), E1 = 0.5 * (C4 - 1.0), E2 = 0.5 * (C8 - 1.0);
+          StVK m = A.mat;
+          if constexpr (TAB) m = StVK{mc[0], mc[1], mc[2]};
+          const double S0 = m.cdiag * E0 + m.lambda * E1 + m.lambda * E2;
+          const double S1 = m.lambda * E0 + m.cdiag * E1 + m.lambda * E2;
+          const double S2 = m.lambda * E0 + m.lambda * E1 + m.cdiag * E2;
+          const double S3 = m.mu * C3, S4 = m.mu * C7, S5 = m.mu * C2;
+          const double sa0 = S0 * na[0] + S3 * na[1] + S5 * na[2];
+          const double sa1 = S3 * na[0] + S1 * na[1] + S4 * na[2];
+          const double sa2 = S5 * na[0] + S4 * na[1] + S2 * na[2];
+          // f_A part: fac F S N_XYZ_A
+          fp0 = fac * (F[0] * sa0 + F[3] * sa1 + F[6] * sa2);
+          fp1 = fac * (F[1] * sa0 + F[4] * sa1 + F[7] * sa2);
+          fp2 = fac * (F[2] * sa0 + F[5] * sa1 + F[8] * sa2);
+          // stage 3 needs, for N_XYZ_b = J^-T dN_b (b_j = sum_dir J[j + 3 dir] d_dir):
+          //   fac F a | J^-T-folded fac S a | Q = F J^-T (Q[i + 3 dir]) | F F^T | J^-T-folded fac a
+          const double fs0 = fac * sa0, fs1 = fac * sa1, fs2 = fac * sa2;
+          const double fa0 = fac * na[0], fa1 = fac * na[1], fa2 = fac * na[2];
+          P[0] = F[0] * fa0 + F[3] * fa1 + F[6] * fa2;
+          P[1] = F[1] * fa0 + F[4] * fa1 + F[7] * fa2;
+          P[2] = F[2] * fa0 + F[5] * fa1 + F[8] * fa2;
+#pragma unroll
+          for (int dir = 0; dir < 3; ++dir)
+          {
+            const double j0 = J[0 + 3 * dir], j1 = J[1 + 3 * dir], j2 = J[2 + 3 * dir];
+            P[3 + dir] = fs0 * j0 + fs1 * j1 + fs2 * j2;
+            P[21 + dir] = fa0 * j0 + fa1 * j1 + fa2 * j2;
+#pragma unroll
+            for (int ii = 0; ii < 3; ++ii) P[6 + ii + 3 * dir] = F[ii] * j0 + F[ii + 3] * j1 + F[ii + 6] * j2;
+          }
+          P[15] = F[0] * F[0] + F[3] * F[3] + F[6] * F[6];
+          P[16] = F[1] * F[1] + F[4] * F[4] + F[7] * F[7];
+          P[17] = F[2] * F[2] + F[5] * F[5] + F[8] * F[8];
+          P[18] = F[0] * F[1] + F[3] * F[4] + F[6] * F[7];
+          P[19] = F[1] * F[2] + F[4] * F[5] + F[7] * F[8];
+          P[20] = F[2] * F[0] + F[5] * F[3] + F[8] * F[6];
+        }
       }
       if (bad)
       {
@@ -523,14 +591,24 @@ __global__ __launch_bounds__(64, 2) void gather_h8_kernel(GatherArgs A)
           G[0] += fpa0 * pb0; G[1] += fpa0 * pb1; G[2] += fpa0 * pb2;
           G[3] += fpa1 * pb0; G[4] += fpa1 * pb1; G[5] += fpa1 * pb2;
           G[6] += fpa2 * pb0; G[7] += fpa2 * pb1; G[8] += fpa2 * pb2;
-          const double t = P[21] * d0 + P[22] * d1 + P[23] * d2;
+          if constexpr (!NH)
+          {
+            const double t = P[21] * d0 + P[22] * d1 + P[23] * d2;
 #pragma unroll
-          for (int k = 0; k < 6; ++k) H[k] += t * P[15 + k];
-          geo += P[3] * d0 + P[4] * d1 + P[5] * d2;
+            for (int k = 0; k < 6; ++k) H[k] += t * P[15 + k];
+          }
+          geo += P[3] * d0 + P[4] * d1 + P[5] * d2;  // StVK a.S.b, CoupNeoHooke a.b
         }
       }
       // G[3 r + c] = sum_g fac (.)_r (.)_c -> K_ab[r + 3 c] = lambda G_rc + mu G_cr (+ I terms)
-      const double lam = TAB ? mc[0] : A.mat.lambda, mu = TAB ? mc[1] : A.mat.mu;
+      double lam = TAB ? mc[0] : A.mat.lambda, mu = TAB ? mc[1] : A.mat.mu;
+      if constexpr (NH)
+      {
+        // lambda0 = 4 c beta, mu0 = 2 c, from the table's c, beta by the uniform case's arithmetic
+        const double nc = TAB ? mc[0] : A.nh_c, nbeta = TAB ? mc[1] : A.nh_beta;
+        lam = (4.0 * nc) * nbeta;
+        mu = 2.0 * nc;
+      }
 #pragma unroll
       for (int rr = 0; rr < 3; ++rr)
 #pragma unroll
@@ -545,6 +623,12 @@ __global__ __launch_bounds__(64, 2) void gather_h8_kernel(GatherArgs A)
         fp0 = Kb[0] * uc[0] + Kb[3] * uc[1] + Kb[6] * uc[2];
         fp1 = Kb[1] * uc[0] + Kb[4] * uc[1] + Kb[7] * uc[2];
         fp2 = Kb[2] * uc[0] + Kb[5] * uc[1] + Kb[8] * uc[2];
+      }
+      else if constexpr (NH)
+      {
+        Kb[0] += mu * geo;
+        Kb[4] += mu * geo;
+        Kb[8] += mu * geo;
       }
       else
       {
@@ -716,6 +800,7 @@ __global__ __launch_bounds__(64, 2) void gather_h8_kernel(GatherArgs A)
   }
 }
 
+#ifndef FCG_GATHER_NEOHOOKE_TU
 // The Gauss points' geometric factors of every element, from its reference coordinates (fixed for
 // the context's lifetime), one thread per (element, Gauss point): J at the point and its inverse
 // (4C_solid_3D_ele_calc_lib.hpp:380-448), fac = det J w, the nodal det J > 0 check at corner g
@@ -789,9 +874,98 @@ __global__ void fold_err_kernel(int32_t* err, int code, int ele)
   atomicMax(&err[0], code);
   atomicMin(&err[1], ele);
 }
+#endif  // FCG_GATHER_NEOHOOKE_TU
+
+GatherArgs gather_args(const DeviceMesh& m, const double* d_u_col, double* d_K, double* d_fint)
+{
+  GatherArgs a{};
+  a.n_single = m.n_rec_single;
+  a.n_multi = m.n_multi;
+  a.multi_ptr = m.multi_ptr;
+  a.rec_row0 = m.rec_row0;
+  a.rec_meta = m.rec_meta;
+  a.rec_base = m.rec_base;
+  a.rec_ele = m.rec_ele;
+  a.rec_a = m.rec_a;
+  a.rec_tmap = m.rec_tmap;
+  a.ele_orig = m.ele_orig;
+  a.ele_x = m.ele_x;
+  a.ele_gp = m.ele_gp;
+  a.ele_dof = m.ele_dof;
+  a.u_col = d_u_col;
+  a.gp = m.tables;
+  a.K = d_K;
+  a.fint = d_fint;
+  a.err = m.err;
+  a.dummy = m.gather_dummy;
+  a.mat = StVK{m.lambda, m.mu, m.cdiag};
+  a.nh_c = m.nh_c;
+  a.nh_beta = m.nh_beta;
+  a.ele_mat = m.ele_mat;
+  return a;
+}
+
+// one-wave workgroups, as many as the LDS keeps resident on every CU, a multiple of the 8 XCDs,
+// each a contiguous block of records / nodes
+// workgroups per CU: two waves per SIMD.  (Linear kinematics would fit nine by LDS and registers
+// since the Gauss-point factors are precomputed -- measured 10 % slower: more streams in L2.)
+#ifndef FCG_GATHER_WPC_LINEAR
+#define FCG_GATHER_WPC_LINEAR 8
+#endif
+dim3 gather_grid(const DeviceMesh& m, int64_t work)
+{
+  const int64_t want = int64_t(256) * (m.kinem == 0 ? FCG_GATHER_WPC_LINEAR : 8);
+  return dim3{static_cast<unsigned>(std::max<int64_t>(8, std::min<int64_t>(want, (work + 7) / 8 * 8))), 1, 1};
+}
+
+// the four (WANT_K, OVERWRITE) instantiations of one (KIN, MULTI, TAB, MAT); expects m, a, want_k,
+// overwrite and stream in scope
+#define FCG_GATHER(KIN, MULTI, WORK, TAB, MAT)                                                               \
+  if ((WORK) > 0)                                                                                            \
+  {                                                                                                          \
+    const dim3 grid = gather_grid(m, WORK), block{64, 1, 1};                                                 \
+    if (want_k && overwrite)                                                                                 \
+      hipLaunchKernelGGL((gather_h8_kernel<KIN, true, true, MULTI, TAB, MAT>), grid, block, 0, stream, a);   \
+    else if (want_k)                                                                                         \
+      hipLaunchKernelGGL((gather_h8_kernel<KIN, true, false, MULTI, TAB, MAT>), grid, block, 0, stream, a);  \
+    else if (overwrite)                                                                                      \
+      hipLaunchKernelGGL((gather_h8_kernel<KIN, false, true, MULTI, TAB, MAT>), grid, block, 0, stream, a);  \
+    else                                                                                                     \
+      hipLaunchKernelGGL((gather_h8_kernel<KIN, false, false, MULTI, TAB, MAT>), grid, block, 0, stream, a); \
+  }
 
 }  // namespace
 
+// The ElastHyper/CoupNeoHooke instantiations live in their own translation unit,
+// fcg_gather_neohooke.hip (this file with FCG_GATHER_NEOHOOKE_TU), compiled without the machine
+// loop-invariant code motion: it hoists the polynomial constants of the double-precision exp and
+// log of p = I3^-beta out of the record loop into some 40 VGPRs that are then live across every
+// stage, and the kernels that form K spill (12-28 bytes of scratch per lane at 256 VGPRs);
+// rematerialised inside the loop they take 218-228 VGPRs and no scratch, below the StVK TotLag
+// instantiations (profiles/neohooke_gather/README.md).
+hipError_t launch_gather_h8_neohooke(const DeviceMesh& m, const double* d_u_col, bool want_k,
+    bool overwrite, double* d_K, double* d_fint, hipStream_t stream);
+
+#ifdef FCG_GATHER_NEOHOOKE_TU
+hipError_t launch_gather_h8_neohooke(const DeviceMesh& m, const double* d_u_col, bool want_k,
+    bool overwrite, double* d_K, double* d_fint, hipStream_t stream)
+{
+  if (m.kinem != 1) return hipErrorInvalidValue;  // TotLag only (check_descriptor)
+  const GatherArgs a = gather_args(m, d_u_col, d_K, d_fint);
+  constexpr int kNH = FCG_MAT_ELASTHYPER_COUPNEOHOOKE;
+  if (m.ele_mat)
+  {
+    FCG_GATHER(1, false, m.n_rec_single, true, kNH)
+    FCG_GATHER(1, true, m.n_multi, true, kNH)
+  }
+  else
+  {
+    FCG_GATHER(1, false, m.n_rec_single, false, kNH)
+    FCG_GATHER(1, true, m.n_multi, false, kNH)
+  }
+  return hipGetLastError();
+}
+#else
 hipError_t gather_precompute(DeviceMesh& m, int64_t n_ele, hipStream_t stream)
 {
   if (n_ele == 0) return hipSuccess;
@@ -824,79 +998,37 @@ hipError_t launch_gather_h8(const DeviceMesh& m, const double* d_u_col, bool wan
   // a nodal / Gauss-point Jacobian failure found when the geometric factors were made is reported
   // by every evaluate, as 4C's element throws on every call
   if (m.gp_bad_code) hipLaunchKernelGGL(fold_err_kernel, dim3(1), dim3(1), 0, stream, m.err, m.gp_bad_code, m.gp_bad_ele);
-  GatherArgs a{};
-  a.n_single = m.n_rec_single;
-  a.n_multi = m.n_multi;
-  a.multi_ptr = m.multi_ptr;
-  a.rec_row0 = m.rec_row0;
-  a.rec_meta = m.rec_meta;
-  a.rec_base = m.rec_base;
-  a.rec_ele = m.rec_ele;
-  a.rec_a = m.rec_a;
-  a.rec_tmap = m.rec_tmap;
-  a.ele_orig = m.ele_orig;
-  a.ele_x = m.ele_x;
-  a.ele_gp = m.ele_gp;
-  a.ele_dof = m.ele_dof;
-  a.u_col = d_u_col;
-  a.gp = m.tables;
-  a.K = d_K;
-  a.fint = d_fint;
-  a.err = m.err;
-  a.dummy = m.gather_dummy;
-  a.mat = StVK{m.lambda, m.mu, m.cdiag};
-  a.ele_mat = m.ele_mat;
-  // one-wave workgroups, as many as the LDS keeps resident on every CU, a multiple of the 8 XCDs,
-  // each a contiguous block of records / nodes
-  // workgroups per CU: two waves per SIMD.  (Linear kinematics would fit nine by LDS and registers
-  // since the Gauss-point factors are precomputed -- measured 10 % slower: more streams in L2.)
-#ifndef FCG_GATHER_WPC_LINEAR
-#define FCG_GATHER_WPC_LINEAR 8
-#endif
-  const int64_t want = int64_t(256) * (m.kinem == 0 ? FCG_GATHER_WPC_LINEAR : 8);
-  const dim3 block{64, 1, 1};
-  auto grid_of = [&](int64_t work) {
-    return dim3{static_cast<unsigned>(std::max<int64_t>(8, std::min<int64_t>(want, (work + 7) / 8 * 8))), 1, 1};
-  };
-#define FCG_GATHER(KIN, MULTI, WORK, TAB)                                                               \
-  if ((WORK) > 0)                                                                                       \
-  {                                                                                                     \
-    const dim3 grid = grid_of(WORK);                                                                    \
-    if (want_k && overwrite)                                                                            \
-      hipLaunchKernelGGL((gather_h8_kernel<KIN, true, true, MULTI, TAB>), grid, block, 0, stream, a);   \
-    else if (want_k)                                                                                    \
-      hipLaunchKernelGGL((gather_h8_kernel<KIN, true, false, MULTI, TAB>), grid, block, 0, stream, a);  \
-    else if (overwrite)                                                                                 \
-      hipLaunchKernelGGL((gather_h8_kernel<KIN, false, true, MULTI, TAB>), grid, block, 0, stream, a);  \
-    else                                                                                                \
-      hipLaunchKernelGGL((gather_h8_kernel<KIN, false, false, MULTI, TAB>), grid, block, 0, stream, a); \
-  }
+  if (m.material == FCG_MAT_ELASTHYPER_COUPNEOHOOKE)
+    return launch_gather_h8_neohooke(m, d_u_col, want_k, overwrite, d_K, d_fint, stream);
+  const GatherArgs a = gather_args(m, d_u_col, d_K, d_fint);
+  constexpr int kStVK = FCG_MAT_STVK;
   // a context with a material table (fcg_set_element_materials) takes the TAB instantiations
   if (m.ele_mat)
   {
     if (m.kinem == 0)
     {
-      FCG_GATHER(0, false, m.n_rec_single, true)
-      FCG_GATHER(0, true, m.n_multi, true)
+      FCG_GATHER(0, false, m.n_rec_single, true, kStVK)
+      FCG_GATHER(0, true, m.n_multi, true, kStVK)
     }
     else
     {
-      FCG_GATHER(1, false, m.n_rec_single, true)
-      FCG_GATHER(1, true, m.n_multi, true)
+      FCG_GATHER(1, false, m.n_rec_single, true, kStVK)
+      FCG_GATHER(1, true, m.n_multi, true, kStVK)
     }
   }
   else if (m.kinem == 0)
   {
-    FCG_GATHER(0, false, m.n_rec_single, false)
-    FCG_GATHER(0, true, m.n_multi, false)
+    FCG_GATHER(0, false, m.n_rec_single, false, kStVK)
+    FCG_GATHER(0, true, m.n_multi, false, kStVK)
   }
   else
   {
-    FCG_GATHER(1, false, m.n_rec_single, false)
-    FCG_GATHER(1, true, m.n_multi, false)
+    FCG_GATHER(1, false, m.n_rec_single, false, kStVK)
+    FCG_GATHER(1, true, m.n_multi, false, kStVK)
   }
-#undef FCG_GATHER
   return hipGetLastError();
 }
+#endif  // FCG_GATHER_NEOHOOKE_TU
+#undef FCG_GATHER
 
 }  // namespace fcg

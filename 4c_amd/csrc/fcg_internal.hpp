@@ -238,8 +238,8 @@ hipError_t launch_h27_apply_plan(const DeviceMesh& m, hipStream_t stream);  // f
 // row-major).  flag: the solver flag word (1: singular or NaN block, 2: a row outside the map).
 hipError_t launch_h27_diag(const DeviceMesh& m, const double* d_u_col, int64_t n_dbc,
     const int32_t* d_dbc_rows, double* d_diag, double* d_dinv, int32_t* flag, hipStream_t stream);
-// Node-row gather (FCG_PATH_GATHER, hex8 StVK on any mesh): one wavefront per owned row node
-// (fcg_gather.hip).
+// Node-row gather (FCG_PATH_GATHER, hex8 StVK or ElastHyper/CoupNeoHooke on any mesh): one
+// wavefront per owned row node (fcg_gather.hip).
 hipError_t gather_precompute(DeviceMesh& m, int64_t n_ele, hipStream_t stream);
 hipError_t launch_gather_h8(const DeviceMesh& m, const double* d_u_col, bool want_k, bool overwrite,
     double* d_K, double* d_fint, hipStream_t stream);

@@ -656,7 +656,10 @@ class BoxMesh:
 
 class Evaluator:
     """Device context (fcg_ctx): the MI355X replacement of Discretization::evaluate for SOLID
-    hex8/hex27 + StVK.  Keeps 4C's error behaviour: a non-zero status raises FcgError."""
+    hex8/hex27 with material=MAT_STVK or MAT_ELASTHYPER_COUPNEOHOOKE (TOTLAG only).  path:
+    PATH_AUTO picks the sweep / gather / general path (hex8 CoupNeoHooke: PATH_GENERAL);
+    PATH_GATHER requests the node-row gather, hex8 with either material.  Keeps 4C's error
+    behaviour: a non-zero status raises FcgError."""
 
     def __init__(self, desc_or_mesh, kinematics=LINEAR, youngs=210.0, poisson=0.3, device=0,
                  path=PATH_AUTO, material=MAT_STVK):
@@ -689,8 +692,8 @@ class Evaluator:
     def set_element_materials(self, youngs, poisson=None, ele_mat=None):
         """fcg_set_element_materials: element e (column-element order) takes youngs[ele_mat[e]],
         poisson[ele_mat[e]] of the context's material kind; set_element_materials(None) returns to
-        the uniform material.  Honoured on PATH_GATHER / PATH_GENERAL (evaluate, tangent_apply,
-        tangent_diag); a PATH_STRUCTURED / PATH_COLORED context raises FcgError (code 3), as do
+        the uniform material.  Honoured on PATH_GATHER (hex8, both materials) / PATH_GENERAL
+        (evaluate, tangent_apply, tangent_diag); a PATH_STRUCTURED / PATH_COLORED context raises FcgError (code 3), as do
         parameters outside the ranges of fcg_create -- the context then stays as it was.  Waits for
         the context's stream; not to be called while evaluates run on other streams."""
         L = lib()

@@ -92,14 +92,16 @@ typedef struct fcg_desc {
    * (hex8) or the colour-ordered direct assembly (hex27) -- no scratch round trip either way.
    * NULL = general (unstructured) path. */
   const int32_t* ele_ijk;
-  int32_t path;                /* fcg_path: FCG_PATH_AUTO / _GENERAL / _STRUCTURED */
+  int32_t path;                /* fcg_path: FCG_PATH_AUTO / _GENERAL / _STRUCTURED / _COLORED / _GATHER */
   int32_t material;            /* fcg_material (0 = StVenantKirchhoff) */
 } fcg_desc;
 
 /* Materials.  FCG_MAT_STVK: MAT_Struct_StVenantKirchhoff YOUNG NUE (4C_mat_stvenantkirchhoff.cpp).
  * FCG_MAT_ELASTHYPER_COUPNEOHOOKE: MAT_ElastHyper with one ELAST_CoupNeoHooke summand, youngs /
  * poisson = the summand's YOUNG / NUE (4C_mat_elasthyper_service.cpp:19-215,
- * 4C_mat_elast_coupneohooke.cpp); FCG_TOTLAG only, general (unstructured) kernels. */
+ * 4C_mat_elast_coupneohooke.cpp); FCG_TOTLAG only.  hex8: FCG_PATH_GENERAL (what FCG_PATH_AUTO
+ * takes) or, on request, FCG_PATH_GATHER; hex27: FCG_PATH_GENERAL or the colour-ordered assembly.
+ * The structured sweep implements StVenantKirchhoff only. */
 enum fcg_material { FCG_MAT_STVK = 0, FCG_MAT_ELASTHYPER_COUPNEOHOOKE = 1 };
 
 /* Evaluation paths.  AUTO picks the hex8 row-block sweep (FCG_PATH_STRUCTURED) when the lattice
@@ -109,7 +111,10 @@ enum fcg_material { FCG_MAT_STVK = 0, FCG_MAT_ELASTHYPER_COUPNEOHOOKE = 1 };
  * in the environment turns the search off); other hex8 StVK meshes take FCG_PATH_GATHER (one wavefront per owned row node
  * recomputes the node's elements and writes its 3 CSR rows once: no scratch, no atomics, any
  * conforming mesh with <= 27 neighbour nodes per node); everything else GENERAL (element kernel +
- * incidence scratch + row assembly).  STRUCTURED requests the lattice path and fails fcg_create with
+ * incidence scratch + row assembly).  GATHER requests the node-row gather explicitly: hex8 only,
+ * StVenantKirchhoff (both kinematics) or ElastHyper/CoupNeoHooke -- AUTO keeps hex8 CoupNeoHooke on
+ * GENERAL, so that material reaches the gather (no incidence scratch, each CSR row written once,
+ * bitwise reproducible, ghosted partitions) only by this request.  STRUCTURED requests the lattice path and fails fcg_create with
  * FCG_ERR_ARG when the hint does not verify: for hex8 the fused row-block sweep, for hex27 the
  * colour-ordered direct assembly (reported as FCG_PATH_COLORED: for StVK four launches of
  * pencils -- runs of elements along x walked by one workgroup each -- in (y, z)-parity colours,
@@ -138,8 +143,8 @@ const char* fcg_last_error(const fcg_ctx* ctx);
  * The constants are formed per material with fcg_create's host arithmetic and stored per element on
  * the device (32 bytes per element, counted in fcg_info.device_bytes), so a table whose entries
  * all equal the context's own material reproduces the uniform results bit for bit.
- * Honoured by the FCG_PATH_GATHER and FCG_PATH_GENERAL kernels (hex8 and hex27, both kinematics,
- * both materials) and by fcg_tangent_apply / fcg_tangent_diag.  A context on FCG_PATH_STRUCTURED
+ * Honoured by the FCG_PATH_GATHER (hex8, both kinematics, both materials) and FCG_PATH_GENERAL
+ * (hex8 and hex27, both kinematics, both materials) kernels and by fcg_tangent_apply / fcg_tangent_diag.  A context on FCG_PATH_STRUCTURED
  * or FCG_PATH_COLORED refuses a table with FCG_ERR_ARG (create it with FCG_PATH_GATHER /
  * FCG_PATH_GENERAL), and fcg_tsi_evaluate_fused refuses a structural context that carries one.
  * The call drains the context's stream before it swaps the tables; it must not run concurrently
