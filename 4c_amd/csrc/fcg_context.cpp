@@ -48,7 +48,7 @@ void free_mesh(fcg::DeviceMesh& m)
       m.ele_dof, m.ele_nodes, m.ele_gid, m.node_x, m.node_dof_col, m.inc_of, m.inc_ptr,
       m.rownode_row0, m.inc_pos, m.rowptr, m.scratch, m.err, m.elem_at, m.lat_x, m.lat_dof,
       m.plane_rec,
-      m.tables, m.stamps, m.col_lid, m.diag_pos, m.pcg_work, m.col_ele, m.ele_ft, m.inc_row0, m.ele_gp,
+      m.tables, m.stamps, m.col_lid, m.diag_pos, m.pcg_work, m.krylov_work, m.col_ele, m.ele_ft, m.inc_row0, m.ele_gp,
       m.pen_ptr, m.ele_nb, m.h27_rows, m.h27_rslot0, m.h27_slot};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);

@@ -155,6 +155,11 @@ struct DeviceMesh {
   // per-workgroup partials of the kinetic energy / the row bound (calls on one context that use
   // it must be stream-ordered, as with pcg_work), then the bound and the lowest refused row
   double* explicit_work = nullptr;   // [kExplicitPartials + 2]
+
+  // FGMRES (fcg_krylov.hip): both bases, the partial sums, the scalar block and the front's
+  // preconditioner blocks, allocated on the first solve and regrown when a solve needs more
+  double* krylov_work = nullptr;
+  int64_t krylov_doubles = 0;
 };
 constexpr int kExplicitPartials = 2048;  // the grid cap of the streaming kernels of fcg_explicit.hip
 

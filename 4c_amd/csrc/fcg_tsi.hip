@@ -44,6 +44,7 @@
 #include "fcg_internal.hpp"
 #include "fcg_status.hpp"
 #include "fcg_shape.hpp"
+#include "fcg_tsi_internal.hpp"
 
 namespace fcg {
 namespace {
@@ -51,38 +52,6 @@ namespace {
 // scratch record of incidence (e, a): K_ST rows [3][npe] | K_TS row [npe][3] | K_TT row [npe] |
 // f_S thermal part [3] | f_T [1]
 __host__ __device__ constexpr int tsi_rec(int npe) { return 7 * npe + 4; }
-
-struct TsiDevice {
-  int npe = 8;
-  int64_t n_ele = 0, n_node = 0, n_rownodes = 0, n_inc = 0;
-  int64_t n_rows_s = 0, n_cols_s = 0, n_rows_t = 0, n_cols_t = 0;
-  int64_t nnz_st = 0, nnz_ts = 0, nnz_tt = 0;
-  double m = 0, T0 = 0, conduct = 0;
-  int32_t* ele_nodes = nullptr;
-  int32_t* ele_gid = nullptr;
-  double* node_x = nullptr;
-  int32_t* dof_col_s = nullptr;
-  int32_t* dof_col_t = nullptr;
-  int32_t* inc_of = nullptr;     // [n_ele][npe]
-  int64_t* inc_ptr = nullptr;    // [n_rownodes + 1]
-  int32_t* rn_srow = nullptr;    // [n_rownodes] first structural row
-  int32_t* rn_trow = nullptr;    // [n_rownodes] thermo row
-  uint16_t* pos_st = nullptr;    // [n_inc][npe] position of node b's thermo column in the k_ST rows
-  uint16_t* pos_ts = nullptr;    // [n_inc][npe] position of node b's displacement triple in the k_TS row
-  uint16_t* pos_tt = nullptr;    // [n_inc][npe] position of node b's thermo column in the k_TT row
-  int64_t* rowptr_st = nullptr;
-  int64_t* rowptr_ts = nullptr;
-  int64_t* rowptr_tt = nullptr;
-  double* tables = nullptr;      // dN at GPs [npe][npe][3] | N at GPs [npe][npe] | dN at nodes | w
-  double* scratch = nullptr;     // [n_inc][tsi_rec(npe)]
-  int32_t* err = nullptr;        // [2]
-  // fused path (fcg_tsi_evaluate_fused): node-consistent numbering verified at create, the
-  // structural context it was last verified against, the k_TT graph on the device for that check
-  bool fusable = false;
-  double lambda = 0, mu = 0;
-  int32_t* col_tt = nullptr;
-  const void* fused_with = nullptr;
-};
 
 template <int NPE>
 struct TsiShared {
@@ -461,14 +430,6 @@ int grid_for(int64_t work, int cap) { return int(work < cap ? (work > 0 ? work :
 }  // namespace
 }  // namespace fcg
 
-struct fcg_tsi_ctx {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  fcg::TsiDevice d;
-  std::string last_error;
-  int64_t device_bytes = 0;
-};
-
 extern "C" {
 
 const char* fcg_tsi_last_error(const fcg_tsi_ctx* ctx)
@@ -485,7 +446,7 @@ int fcg_tsi_destroy(fcg_tsi_ctx* ctx)
   fcg::TsiDevice& d = ctx->d;
   void* ptrs[] = {d.ele_nodes, d.ele_gid, d.node_x, d.dof_col_s, d.dof_col_t, d.inc_of, d.inc_ptr,
       d.rn_srow, d.rn_trow, d.pos_st, d.pos_ts, d.pos_tt, d.rowptr_st, d.rowptr_ts, d.rowptr_tt,
-      d.tables, d.scratch, d.err, d.col_tt};
+      d.tables, d.scratch, d.err, d.col_tt, d.krylov_work};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
@@ -653,7 +614,8 @@ int fcg_tsi_create(const fcg_tsi_desc* D, fcg_tsi_ctx** out)
 
   // node-consistent numbering (what fcg_tsi_evaluate_fused requires): thermo DOF LIDs are the
   // structural ones / 3 and the three block graphs are expansions of one node graph (the k_TT graph)
-  bool fusable = npe == 8 && D->n_rows_s == 3 * D->n_rows_t && D->n_cols_s == 3 * D->n_cols_t;
+  // (hex8 and hex27: the block operator and its solve take both; the fused evaluate is hex8's)
+  bool fusable = D->n_rows_s == 3 * D->n_rows_t && D->n_cols_s == 3 * D->n_cols_t;
   for (int64_t n = 0; fusable && n < D->n_node; ++n)
     fusable = D->node_dof_col_s[n] == 3 * D->node_dof_col_t[n] &&
               D->node_dof_row_s[n] == (D->node_dof_row_t[n] < 0 ? D->node_dof_row_s[n] : 3 * D->node_dof_row_t[n]);
@@ -703,7 +665,8 @@ int fcg_tsi_create(const fcg_tsi_desc* D, fcg_tsi_ctx** out)
     d.lambda = lambda;
     d.mu = mu;
   }
-  d.fusable = fusable;
+  d.node_consistent = fusable;
+  d.fusable = fusable && npe == 8;
   d.T0 = D->inittemp;
   d.conduct = D->conduct;
   std::vector<int32_t> eg;

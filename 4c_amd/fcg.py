@@ -131,6 +131,13 @@ class FcgAmgOptions(ctypes.Structure):
                 ("ratio", ctypes.c_double), ("boost", ctypes.c_double)]
 
 
+class FcgGmresOptions(ctypes.Structure):
+    """fcg_gmres_options (include/fourc_gpu.h)."""
+    _fields_ = [("restart", ctypes.c_int32), ("max_iter", ctypes.c_int32),
+                ("rtol", ctypes.c_double), ("precond", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
 EXPORTS = ["fcg_create", "fcg_destroy", "fcg_last_error", "fcg_evaluate", "fcg_evaluate_device",
            "fcg_device_alloc", "fcg_device_free", "fcg_memcpy_h2d", "fcg_memcpy_d2h",
            "fcg_memset_device", "fcg_set_timing", "fcg_get_timing", "fcg_get_info",
@@ -158,7 +165,10 @@ EXPORTS = ["fcg_create", "fcg_destroy", "fcg_last_error", "fcg_evaluate", "fcg_e
            "fcg_transport_rccl", "fcg_dfcg_solve",
            "fcg_mass_assemble", "fcg_mass_nodal", "fcg_effective_tangent",
            "fcg_gp_stress", "fcg_gp_to_nodes",
-           "fcg_centrdiff_step", "fcg_stable_dt"]
+           "fcg_centrdiff_step", "fcg_stable_dt",
+           "fcg_gmres_default_options", "fcg_gmres_solve", "fcg_gmres_set_timing",
+           "fcg_gmres_get_timing", "fcg_gmres_orthogonalize_work", "fcg_gmres_orthogonalize",
+           "fcg_tsi_block_apply", "fcg_tsi_dirichlet_apply", "fcg_tsi_gmres_solve"]
 
 _lib = None
 FUNCT_FN = ctypes.CFUNCTYPE(ctypes.c_double, ctypes.c_int, _dp, ctypes.c_double, ctypes.c_void_p)
@@ -326,6 +336,19 @@ def lib():
     L.fcg_gp_to_nodes.argtypes = [vp, vp, vp, vp]
     L.fcg_centrdiff_step.argtypes = [vp, c_dbl, c_dbl, c_dbl, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.fcg_stable_dt.argtypes = [vp, vp, vp, vp, _dp, _dp, vp]
+    L.fcg_gmres_default_options.argtypes = [ctypes.POINTER(FcgGmresOptions)]
+    L.fcg_gmres_default_options.restype = None
+    L.fcg_gmres_solve.argtypes = [vp, vp, vp, vp, vp, ctypes.POINTER(FcgGmresOptions),
+                                  ctypes.POINTER(c_int), _dp, vp]
+    L.fcg_gmres_orthogonalize_work.argtypes = [i64, c_int]
+    L.fcg_gmres_orthogonalize_work.restype = i64
+    L.fcg_gmres_orthogonalize.argtypes = [c_int, i64, c_int, vp, i64, vp, vp, vp, vp]
+    L.fcg_gmres_set_timing.argtypes = [c_int]
+    L.fcg_gmres_get_timing.argtypes = [_dp, _dp, _dp, _i64p]
+    L.fcg_tsi_block_apply.argtypes = [vp] * 11
+    L.fcg_tsi_dirichlet_apply.argtypes = [vp, i64, vp, i64, vp, vp, vp, vp, vp, vp]
+    L.fcg_tsi_gmres_solve.argtypes = [vp] * 11 + [ctypes.POINTER(FcgGmresOptions),
+                                                  ctypes.POINTER(c_int), _dp, vp]
     _lib = L
     return L
 
@@ -851,6 +874,22 @@ class Evaluator:
             self._raise(rc, -1)
         return it.value, rr.value
 
+    def gmres_solve(self, K_vals, b, x, rtol=1e-10, max_iter=10000, restart=50, amg=None,
+                    stream=None):
+        """K x = b for any values on the context's graph (symmetry is not assumed) by restarted
+        flexible GMRES from x = 0 (fcg_gmres_solve); the preconditioner is the nodal block Jacobi,
+        or one cycle of `amg` (an amg.NativeAMG whose setup(K) the caller has run).  Returns
+        (inner steps taken, true relative residual)."""
+        opt = gmres_options(restart, max_iter, rtol)
+        it, rr = ctypes.c_int(0), ctypes.c_double(0.0)
+        rc = lib().fcg_gmres_solve(self._h, amg._h if amg is not None else None,
+                                   _tensor_ptr(K_vals), _tensor_ptr(b), _tensor_ptr(x),
+                                   ctypes.byref(opt), ctypes.byref(it), ctypes.byref(rr),
+                                   self._stream(stream))
+        if rc != 0:
+            self._raise(rc, -1)
+        return it.value, rr.value
+
     def _ele_density(self, ele_density):
         if ele_density is None:
             return None, None
@@ -1018,6 +1057,55 @@ class Evaluator:
         return a.value, b.value
 
 
+def gmres_options(restart=None, max_iter=None, rtol=None, precond=None):
+    """fcg_gmres_options: the library's defaults with the given fields replaced."""
+    opt = FcgGmresOptions()
+    lib().fcg_gmres_default_options(ctypes.byref(opt))
+    for k, v in (("restart", restart), ("max_iter", max_iter), ("precond", precond)):
+        if v is not None:
+            setattr(opt, k, int(v))
+    if rtol is not None:
+        opt.rtol = float(rtol)
+    return opt
+
+
+def gmres_orthogonalize(V, w, h, work=None, stream=None):
+    """fcg_gmres_orthogonalize on torch tensors: V [nv][ld] float64 (ld even, rows are the basis
+    vectors, n = w.numel() <= ld), w [n] orthogonalised in place against them, h [nv + 1] the
+    coefficients and |w|.  work: a float64 tensor of gmres_orthogonalize_work(n, nv) doubles
+    (allocated when None).  Asynchronous."""
+    import torch
+    nv, ld, n = int(V.shape[0]), int(V.shape[1]), int(w.numel())
+    if work is None:
+        work = torch.empty(gmres_orthogonalize_work(n, nv), dtype=torch.float64, device=w.device)
+    rc = lib().fcg_gmres_orthogonalize(w.device.index or 0, n, nv, _tensor_ptr(V), ld, _tensor_ptr(w),
+                                       _tensor_ptr(h), _tensor_ptr(work),
+                                       _torch_stream(stream, w.device))
+    if rc != 0:
+        raise FcgError(rc, "fcg_gmres_orthogonalize failed")
+    return work
+
+
+def gmres_orthogonalize_work(n, nv):
+    k = lib().fcg_gmres_orthogonalize_work(int(n), int(nv))
+    if k < 0:
+        raise FcgError(3, "fcg_gmres_orthogonalize_work: bad n or nv")
+    return int(k)
+
+
+def gmres_timing(enable=None):
+    """fcg_gmres_set_timing(enable) when `enable` is given; else the sums since it was set:
+    {"precond_ms", "operator_ms", "orth_ms", "steps"} over the inner steps launched."""
+    if enable is not None:
+        rc = lib().fcg_gmres_set_timing(1 if enable else 0)
+        if rc != 0:
+            raise FcgError(rc, "fcg_gmres_set_timing failed")
+        return None
+    a, b, c, n = ctypes.c_double(), ctypes.c_double(), ctypes.c_double(), ctypes.c_int64()
+    lib().fcg_gmres_get_timing(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(n))
+    return {"precond_ms": a.value, "operator_ms": b.value, "orth_ms": c.value, "steps": n.value}
+
+
 class TsiGraph:
     """The thermo field of a rank for TSI: one temperature DOF per node of the cloned thermo
     discretization (same nodes, elements and owners as the structure; thermo DOF GIDs follow the
@@ -1123,6 +1211,53 @@ class TsiEvaluator:
                                           _tensor_ptr(Kts), s, ctypes.byref(bad))
         if rc != 0:
             raise FcgError(rc, lib().fcg_tsi_last_error(self._h).decode(), bad.value)
+
+
+    def _fail(self, rc):
+        raise FcgError(rc, lib().fcg_tsi_last_error(self._h).decode())
+
+    def block_apply(self, struct_ev, Kss, Kst, Kts, Ktt, xs, xt, ys, yt, stream=None):
+        """fcg_tsi_block_apply: y_S = K_SS x_S + K_ST x_T, y_T = K_TS x_S + K_TT x_T in one kernel
+        (asynchronous); `struct_ev` is the structural Evaluator of the mesh."""
+        rc = lib().fcg_tsi_block_apply(struct_ev._h, self._h, *[_tensor_ptr(a) for a in
+                                       (Kss, Kst, Kts, Ktt, xs, xt, ys, yt)],
+                                       _torch_stream(stream, self.device))
+        if rc != 0:
+            self._fail(rc)
+
+    def dirichlet_apply(self, rows_s=None, rows_t=None, Kst=None, Kts=None, Ktt=None, rhs_T=None,
+                        stream=None):
+        """fcg_tsi_dirichlet_apply: rows_s / rows_t are int32 device tensors of structural /
+        thermal Dirichlet row LIDs (either may be None); K_ST rows_s and K_TS rows_t become zero
+        rows, K_TT rows_t unit rows, rhs_T 0 there.  K_SS and rhs_S go through the structural
+        Evaluator's dirichlet_apply."""
+        ns = 0 if rows_s is None else int(rows_s.numel())
+        nt = 0 if rows_t is None else int(rows_t.numel())
+        rc = lib().fcg_tsi_dirichlet_apply(self._h, ns, _tensor_ptr(rows_s) if ns else None, nt,
+                                           _tensor_ptr(rows_t) if nt else None, _tensor_ptr(Kst),
+                                           _tensor_ptr(Kts), _tensor_ptr(Ktt), _tensor_ptr(rhs_T),
+                                           _torch_stream(stream, self.device))
+        if rc != 0:
+            self._fail(rc)
+
+    PRECOND = {"diag": 0, "bgs": 1, 0: 0, 1: 1}
+
+    def gmres_solve(self, struct_ev, Kss, Kst, Kts, Ktt, bs, bt, xs, xt, rtol=1e-10,
+                    max_iter=10000, restart=50, precond="bgs", amg=None, stream=None):
+        """fcg_tsi_gmres_solve: the monolithic system by restarted flexible GMRES on [x_S; x_T]
+        from x = 0.  precond: "diag" (block diagonal) or "bgs" (block Gauss-Seidel); the
+        structural block is the nodal block Jacobi of K_SS or one cycle of `amg` (an
+        amg.NativeAMG set up on K_SS), the thermal one the diagonal of K_TT.  Returns (inner steps
+        taken, true relative residual of the stacked system)."""
+        opt = gmres_options(restart, max_iter, rtol, self.PRECOND[precond])
+        it, rr = ctypes.c_int(0), ctypes.c_double(0.0)
+        rc = lib().fcg_tsi_gmres_solve(struct_ev._h, self._h, amg._h if amg is not None else None,
+                                       *[_tensor_ptr(a) for a in (Kss, Kst, Kts, Ktt, bs, bt, xs, xt)],
+                                       ctypes.byref(opt), ctypes.byref(it), ctypes.byref(rr),
+                                       _torch_stream(stream, self.device))
+        if rc != 0:
+            self._fail(rc)
+        return it.value, rr.value
 
 
 def graph_build_device(celltype, ele_nodes, node_dof_col, node_dof_row, n_rows, device=0,

@@ -1,0 +1,124 @@
+"""Static monolithic thermo-structure interaction with every vector and matrix resident in HBM:
+the Newton loop of TSI::Monolithic (4C_tsi_monolithic.cpp: newton_full, setup_system_matrix,
+linear_solve) around the library's TSI evaluates, Dirichlet applies and the FGMRES solve of the
+non-symmetric block system [[K_SS, K_ST], [K_TS, K_TT]] (fcg_tsi_gmres_solve).
+
+Both fields are statics with linear kinematics (what fcg_tsi_evaluate_* covers): per time step the
+loads are taken at t_{n+1}; per Newton iteration the velocity of the quasi-static structure is
+v = (d - d_n) / dt (TSI::Algorithm::calc_velocity), the blocks are evaluated with timefac 1 and
+timefac_d 1 / dt, r = f_int - f_ext, the Dirichlet rows are applied to all four blocks and both
+residuals, the increment solves K dx = -r and x += dx.  The iteration stops when
+|dx| <= tol_inc max(1, |x|) on the stacked vector."""
+
+import torch
+
+from . import fcg
+
+
+class TsiMonolithic:
+    """struct_ev / tsi_ev: the structural Evaluator (linear kinematics, StVK with the TSI
+    material's E and nu) and the TsiEvaluator of one single-rank mesh with node-consistent thermo
+    numbering.  fext_s / fext_t: row vectors (tensors or arrays) or callables t -> vector.
+    dbc_s / dbc_t: homogeneous Dirichlet row LIDs of the two fields.  fused: one
+    fcg_tsi_evaluate_fused per iteration (True), two evaluates (False), or fused when the contexts
+    qualify (None).  precond: "bgs" or "diag"; amg: an amg.NativeAMG of struct_ev for the
+    structural block (set up on every K_SS), None: nodal block Jacobi.
+
+    step() advances one time step, run(nstep) several; `history` holds per step the Newton
+    iterations and per solve the GMRES iterations and relative residual.  Raises RuntimeError when
+    Newton or a linear solve misses its tolerance."""
+
+    def __init__(self, struct_ev, tsi_ev, dt, fext_s, fext_t, dbc_s, dbc_t, T_init=None, fused=None,
+                 tol_inc=1e-13, max_iter=30, lin_rtol=1e-10, restart=50, lin_max_iter=2000,
+                 precond="bgs", amg=None):
+        self.sev, self.tev, self.dt = struct_ev, tsi_ev, float(dt)
+        self.dev = torch.device("cuda", struct_ev.device)
+        g = tsi_ev.graph
+        self.ns, self.nt = int(struct_ev.info.n_rows), int(g.n_rows_t)
+        self.fext_s, self.fext_t = fext_s, fext_t
+        i32 = lambda a: torch.as_tensor(a).to(device=self.dev, dtype=torch.int32).contiguous()
+        self.dbc_s, self.dbc_t = i32(dbc_s), i32(dbc_t)
+        self.fused = fused
+        self.tol_inc, self.max_iter = float(tol_inc), int(max_iter)
+        self.lin_rtol, self.restart, self.lin_max_iter = float(lin_rtol), int(restart), int(lin_max_iter)
+        self.precond, self.amg = precond, amg
+        if amg is not None:
+            amg.check_dirichlet(self.dbc_s.cpu().numpy())
+        z = lambda n: torch.zeros(int(n), dtype=torch.float64, device=self.dev)
+        self.d, self.T = z(self.ns), z(self.nt)
+        if T_init is not None:
+            self.T.copy_(self._vec(T_init))
+        self.d_n, self.v = z(self.ns), z(self.ns)
+        self.fs, self.fT = z(self.ns), z(self.nt)
+        self.dxs, self.dxt = z(self.ns), z(self.nt)
+        self.Kss, self.Kst = z(struct_ev.info.nnz), z(g.nnz_st)
+        self.Kts, self.Ktt = z(g.nnz_ts), z(g.nnz_tt)
+        self.step_no, self.t = 0, 0.0
+        self.history = []
+
+    def _vec(self, a):
+        return torch.as_tensor(a).to(device=self.dev, dtype=torch.float64).contiguous()
+
+    def _load(self, f, t):
+        return self._vec(f(t) if callable(f) else f)
+
+    def _evaluate(self):
+        if self.fused is not False:
+            try:
+                self.tev.evaluate_fused(self.sev, fcg.OVERWRITE, self.d, self.v, self.T, 1.0,
+                                        1.0 / self.dt, fs=self.fs, Kss=self.Kss, Kst=self.Kst,
+                                        fT=self.fT, Ktt=self.Ktt, Kts=self.Kts)
+                self.fused = True
+                return
+            except fcg.FcgError as e:
+                if self.fused is True or e.code != 3:
+                    raise
+                self.fused = False  # the contexts do not qualify: two evaluates from now on
+        self.sev.evaluate_device(fcg.CALC_NLNSTIFF, fcg.OVERWRITE, self.d, self.fs, self.Kss)
+        self.tev.evaluate_device(fcg.TSI_ALL, fcg.OVERWRITE, self.v, self.T, 1.0, 1.0 / self.dt,
+                                 fs=self.fs, Kst=self.Kst, fT=self.fT, Ktt=self.Ktt, Kts=self.Kts)
+
+    def step(self):
+        self.step_no += 1
+        self.t = self.step_no * self.dt
+        fes, fet = self._load(self.fext_s, self.t), self._load(self.fext_t, self.t)
+        self.d_n.copy_(self.d)
+        rec = {"step": self.step_no, "iterations": 0, "gmres_iterations": [], "gmres_rel_residual": []}
+        for it in range(self.max_iter):
+            torch.sub(self.d, self.d_n, out=self.v)
+            self.v.div_(self.dt)
+            self._evaluate()
+            # b = -(f_int - f_ext), zero on the Dirichlet rows
+            self.fs.sub_(fes).neg_()
+            self.fT.sub_(fet).neg_()
+            self.sev.dirichlet_apply(self.dbc_s, self.Kss, self.fs)
+            self.tev.dirichlet_apply(self.dbc_s, self.dbc_t, self.Kst, self.Kts, self.Ktt, self.fT)
+            if self.amg is not None:
+                self.amg.setup(self.Kss)
+            n, rel = self.tev.gmres_solve(self.sev, self.Kss, self.Kst, self.Kts, self.Ktt, self.fs,
+                                          self.fT, self.dxs, self.dxt, rtol=self.lin_rtol,
+                                          max_iter=self.lin_max_iter, restart=self.restart,
+                                          precond=self.precond, amg=self.amg)
+            rec["gmres_iterations"].append(n)
+            rec["gmres_rel_residual"].append(rel)
+            if not rel <= self.lin_rtol:
+                self.history.append(rec)
+                raise RuntimeError(f"TSI step {self.step_no}: GMRES stopped at relative residual "
+                                   f"{rel:.3e} > {self.lin_rtol:.1e} after {n} iterations")
+            self.d.add_(self.dxs)
+            self.T.add_(self.dxt)
+            rec["iterations"] = it + 1
+            ninc = torch.sqrt(self.dxs.dot(self.dxs) + self.dxt.dot(self.dxt)).item()
+            nx = torch.sqrt(self.d.dot(self.d) + self.T.dot(self.T)).item()
+            if ninc <= self.tol_inc * max(1.0, nx):
+                break
+        else:
+            self.history.append(rec)
+            raise RuntimeError(f"TSI Newton did not converge in step {self.step_no}")
+        self.history.append(rec)
+        return rec
+
+    def run(self, nstep):
+        for _ in range(int(nstep)):
+            self.step()
+        return self.d, self.T

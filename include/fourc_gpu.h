@@ -601,6 +601,60 @@ int fcg_graph_build_device(int device, int celltype, int64_t n_ele, const int32_
     int64_t* d_rowptr, int32_t* d_col_lid, int64_t col_capacity, int64_t* nnz, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Non-symmetric systems: restarted flexible GMRES (fcg_krylov.hip).  Right-preconditioned
+ * FGMRES(restart) from x = 0 with twice-applied classical Gram-Schmidt; both bases are stored
+ * (restart + 1 vectors V, restart vectors Z), so any preconditioner -- an inexact multigrid cycle
+ * included -- is admissible.  Stops when the Givens estimate of |r| falls to rtol |b|; the true
+ * residual b - A x is recomputed at every restart and before returning, and `rel_residual` is
+ * that true |b - A x| / |b|.  The host reads the device's scalar block once per burst of 8 inner
+ * steps; steps after convergence or an exact breakdown are no-ops, and `iterations` counts the
+ * inner steps actually taken (it may pass the first converged step by fewer than 8).  Every sum
+ * runs in a fixed order (no atomics on doubles): two solves of one system give bitwise equal x.
+ *   restart in [1, 128], max_iter >= 0, rtol >= 0, else FCG_ERR_ARG
+ *   precond   fcg_tsi_gmres_solve: 0 block diagonal, 1 block Gauss-Seidel; ignored here
+ * Reaching max_iter returns FCG_OK with the true rel_residual, as fcg_pcg_solve does.  Non-finite
+ * b, Hessenberg entry or residual, or a singular Hessenberg matrix: FCG_ERR_SINGULAR.  Work space
+ * ((2 restart + 1) n doubles, the partial sums and the preconditioner's blocks) is allocated on
+ * the context at the first solve, reused, freed by the destroy call and counted in device_bytes;
+ * solves on one context must not run concurrently.  Blocking.
+ *
+ * fcg_gmres_solve: K x = b for any values on the context's CSR graph (symmetry is not assumed), on
+ * a single-rank context whose rows are node DOF triples (else FCG_ERR_ARG, as fcg_pcg_solve).
+ * amg NULL: the 3 x 3 nodal block Jacobi of fcg_block_jacobi_setup (FCG_ERR_SINGULAR for a
+ * singular block); else one fcg_amg_apply per step -- the caller has run fcg_amg_setup on this K
+ * (without it fcg_amg_apply's own error is returned).  With the unit rows of fcg_dirichlet_apply
+ * and b = 0 on them, x comes back exactly 0.0 there.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct fcg_gmres_options {
+  int32_t restart;   /* inner steps per cycle (50) */
+  int32_t max_iter;  /* inner steps in all (10000) */
+  double rtol;       /* |r| <= rtol |b| (1e-10) */
+  int32_t precond;   /* fcg_tsi_gmres_solve: 0 block diagonal, 1 block Gauss-Seidel (1) */
+  int32_t reserved;
+} fcg_gmres_options;
+void fcg_gmres_default_options(fcg_gmres_options* opt);
+/* Measurement aid (tools/tsi_solve_bench.py), per process and not thread-safe: while enabled, every
+ * FGMRES solve records hipEvents around the preconditioner, the operator and the orthogonalisation
+ * (Gram-Schmidt, scalar step, scaling) of each inner step it launches, the no-op steps after
+ * convergence included; fcg_gmres_get_timing returns the sums (ms) and the step count since
+ * fcg_gmres_set_timing was last called.  The events are created on the device current at enable. */
+int fcg_gmres_set_timing(int enable);
+int fcg_gmres_get_timing(double* ms_precond, double* ms_operator, double* ms_orth, int64_t* steps);
+/* One orthogonalisation of the solver on its own, with its kernels (for tests and measurement):
+ * w is orthogonalised against the nv vectors d_V + i ld, i < nv, by classical Gram-Schmidt applied
+ * twice -- per pass h'_i = v_i . w for all i (one kernel, block partials, fixed-order second
+ * stage), then w -= sum_i h'_i v_i -- and d_h receives [nv + 1]: the sums h_i of both passes'
+ * coefficients, then |w| of the new w (w is not scaled).  d_V and d_w 16-byte aligned, ld >= n
+ * and even, 1 <= nv <= 128, d_work of fcg_gmres_orthogonalize_work(n, nv) doubles (-1: bad
+ * arguments); else FCG_ERR_ARG.  Deterministic, asynchronous on `stream`. */
+int64_t fcg_gmres_orthogonalize_work(int64_t n, int nv);
+int fcg_gmres_orthogonalize(int device, int64_t n, int nv, const double* d_V, int64_t ld, double* d_w,
+    double* d_h, double* d_work, void* stream);
+int fcg_gmres_solve(fcg_ctx* ctx, fcg_amg* amg_or_null, const double* d_K_vals,
+    const double* d_b_row, double* d_x_row, const fcg_gmres_options* opt, int* iterations,
+    double* rel_residual, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Thermo-structure interaction (TSI), geometrically linear: the temperature-dependent blocks of
  * 4C's monolithic TSI system (TSI::Monolithic, src/tsi/4C_tsi_monolithic.cpp:982-1005, 1694-1869)
  * for SOLIDSCATRA hex8/hex27 elements with MAT_Struct_ThermoStVenantK (constant Young's modulus)
@@ -686,6 +740,44 @@ int fcg_tsi_evaluate_fused(fcg_ctx* sctx, fcg_tsi_ctx* ctx, int mode, const doub
     const double* d_v_col, const double* d_T_col, double timefac, double timefac_d,
     double* d_fs_row, double* d_Kss, double* d_Kst, double* d_fT_row, double* d_Ktt,
     double* d_Kts, void* stream, int32_t* bad_ele_gid);
+/*
+ * The monolithic system [[K_SS, K_ST], [K_TS, K_TT]] on the device (fcg_tsi_solve.hip): what 4C
+ * hands to Belos GMRES with a 2 x 2 block preconditioner (TSI::Monolithic::linear_solve).
+ * All three calls need a TSI context with node-consistent numbering (thermo LID = structural
+ * LID / 3, the three block graphs expansions of the k_TT node graph; hex8 or hex27) on a single
+ * rank (n_cols = n_rows in both fields); the two that take sctx need it on the same device, single
+ * rank, with a CSR graph that is the 3 x 3 expansion of the k_TT graph (checked on the device at
+ * the first call with that context and cached).  Anything else: FCG_ERR_ARG, and
+ * fcg_tsi_last_error names the condition.
+ *
+ * fcg_tsi_block_apply: y_S = K_SS x_S + K_ST x_T, y_T = K_TS x_S + K_TT x_T in one kernel: a
+ * group of lanes per owned node walks the node's k_TT neighbour list once (up to 125 neighbours)
+ * and reads the 9 + 3 + 3 + 1 values and the neighbour's four unknowns; the four row sums are
+ * reduced across the lanes in a fixed order.  Deterministic, asynchronous on `stream`.
+ *
+ * fcg_tsi_dirichlet_apply: the structural Dirichlet rows of K_ST and the thermal Dirichlet rows
+ * of K_TS become zero rows, the thermal ones of K_TT unit rows, rhs_T is set to 0 there; columns
+ * stay (K_SS and rhs_S go through fcg_dirichlet_apply on the structural context).  Any value
+ * pointer may be NULL.  A row outside the map or a thermal row without a diagonal entry:
+ * FCG_ERR_ARG (the other rows are still applied).  Blocking.
+ *
+ * fcg_tsi_gmres_solve: FGMRES (above) on the stacked vector [x_S; x_T] with the block apply as
+ * operator and the 2-norm of the stacked residual as stopping norm.  P_S is the nodal block Jacobi
+ * of K_SS, or fcg_amg_apply on amg_s (set up on K_SS by the caller); D_TT the diagonal of K_TT (a
+ * zero, missing or non-finite entry: FCG_ERR_SINGULAR).  opt->precond 0: z_S = P_S r_S,
+ * z_T = D_TT^-1 r_T; 1 (block Gauss-Seidel, the BGS of 4C's 2 x 2 block preconditioners):
+ * z_S = P_S r_S, z_T = D_TT^-1 (r_T - K_TS z_S), one pass over K_TS fused with the scaling.
+ */
+int fcg_tsi_block_apply(fcg_ctx* sctx, fcg_tsi_ctx* tctx, const double* d_Kss, const double* d_Kst,
+    const double* d_Kts, const double* d_Ktt, const double* d_xs, const double* d_xt, double* d_ys,
+    double* d_yt, void* stream);
+int fcg_tsi_dirichlet_apply(fcg_tsi_ctx* tctx, int64_t n_dbc_s, const int32_t* d_rows_s,
+    int64_t n_dbc_t, const int32_t* d_rows_t, double* d_Kst, double* d_Kts, double* d_Ktt,
+    double* d_rhs_T, void* stream);
+int fcg_tsi_gmres_solve(fcg_ctx* sctx, fcg_tsi_ctx* tctx, fcg_amg* amg_s_or_null,
+    const double* d_Kss, const double* d_Kst, const double* d_Kts, const double* d_Ktt,
+    const double* d_bs, const double* d_bt, double* d_xs, double* d_xt,
+    const fcg_gmres_options* opt, int* iterations, double* rel_residual, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Structured-box discretization builder: a restatement of 4C's GridGenerator

@@ -135,6 +135,28 @@ class Discretization {
     run(params, systemmatrix1, nullptr, systemvector1, nullptr, nullptr, FCG_OVERWRITE);
   }
 
+  /* The linear solve of a tangent that need not be symmetric, K x = b from x = 0 by restarted
+   * flexible GMRES (fcg_gmres_solve; Belos' GMRES in 4C): device views of the graph's values and
+   * of two row vectors; amg: a set-up fcg_amg of this context as preconditioner, nullptr: nodal
+   * block Jacobi.  Returns the inner steps taken; *rel_residual: the true |b - K x| / |b|. */
+  int gmres_solve(const SparseMatrixView& K, const VectorView& b, VectorView& x,
+      const fcg_gmres_options* options = nullptr, fcg_amg* amg = nullptr,
+      double* rel_residual = nullptr, void* stream = nullptr)
+  {
+    if (!K.device || !b.device || !x.device)
+      throw Exception(FCG_ERR_ARG, "gmres_solve takes device views");
+    if (K.nnz != nnz_ || b.length != n_rows_ || x.length != n_rows_)
+      throw Exception(FCG_ERR_ARG, "gmres_solve: sizes differ from the graph's");
+    fcg_gmres_options opt;
+    fcg_gmres_default_options(&opt);
+    if (options) opt = *options;
+    int iterations = 0;
+    const int rc = fcg_gmres_solve(ctx_, amg, K.values, b.values, x.values, &opt, &iterations,
+        rel_residual, stream);
+    if (rc != FCG_OK) throw Exception(rc, fcg_last_error(ctx_));
+    return iterations;
+  }
+
   fcg_ctx* handle() const { return ctx_; }
   int64_t num_rows() const { return n_rows_; }
   int64_t num_cols() const { return n_cols_; }
