@@ -496,3 +496,103 @@ class NativeAMG:
         if rc != 0:
             raise fcg.FcgError(rc, L.fcg_amg_last_error(self._h).decode())
         return it.value, rel.value
+
+
+class ScalarAMG:
+    """Scalar smoothed-aggregation AMG of K_TT as one native object (fcg_samg_create / _setup /
+    _apply / _solve; fcg_samg_plan.cpp, fcg_samg.hip): one DOF per node, the constant as near-null
+    space.  `tev` is a single-rank fcg.TsiEvaluator, dbc_rows_t the thermal Dirichlet rows (unit
+    rows of K_TT).  The thermal block of the monolithic TSI preconditioner
+    (TsiEvaluator.gmres_solve(amg_t=...), tsi.TsiMonolithic(amg_t=...)) and a solver for a
+    conduction problem on its own.  opts: the fields of fcg_amg_options (defaults of
+    fcg_samg_default_options: the structural ones with coarse_max = 300 rows)."""
+
+    def __init__(self, tev, dbc_rows_t, **opts):
+        L = fcg.lib()
+        g = tev.graph
+        self.tev, self.dev = tev, torch.device("cuda", tev.device)
+        self.rows = np.sort(np.asarray(dbc_rows_t, dtype=np.int32))
+        self._rowptr = np.ascontiguousarray(g.rowptr_tt, dtype=np.int64)
+        self._col = np.ascontiguousarray(g.col_tt, dtype=np.int32)
+        self.opt = fcg.FcgAmgOptions()
+        L.fcg_samg_default_options(ctypes.byref(self.opt))
+        for k, v in opts.items():
+            setattr(self.opt, k, v)
+        h = ctypes.c_void_p()
+        rc = L.fcg_samg_create(tev._h, _vp(self._rowptr), _vp(self._col), len(self.rows),
+                               _vp(self.rows), ctypes.byref(self.opt), ctypes.byref(h))
+        if rc != 0:
+            raise fcg.FcgError(rc, L.fcg_tsi_last_error(tev._h).decode())
+        self._h = h
+        self.setup_ms = []
+
+    def close(self):
+        if getattr(self, "_h", None):
+            fcg.lib().fcg_samg_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _fail(self, rc):
+        raise fcg.FcgError(rc, fcg.lib().fcg_samg_last_error(self._h).decode())
+
+    def _stream(self):
+        return ctypes.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
+
+    def check_dirichlet(self, dbc_rows_t):
+        theirs = np.sort(np.asarray(dbc_rows_t, dtype=np.int32))
+        if not np.array_equal(self.rows, theirs):
+            raise ValueError("ScalarAMG Dirichlet rows differ from the system's")
+
+    def describe(self):
+        L = fcg.lib()
+        out = []
+        for l in range(L.fcg_samg_levels(self._h)):
+            r, z, lm = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_double()
+            L.fcg_samg_level_info(self._h, l, ctypes.byref(r), ctypes.byref(z), ctypes.byref(lm))
+            out.append({"level": l, "rows": r.value, "nnz": z.value, "lmax": lm.value,
+                        "setup_ms": L.fcg_samg_setup_ms(self._h, l)})
+        return out
+
+    def level_matrix(self, level, which):
+        """(ptr, col, vals) of A_level (which = 0) or P_level (which = 1) after the last setup."""
+        L = fcg.lib()
+        nnz = L.fcg_samg_level_matrix(self._h, level, which, None, None, None, 0)
+        if nnz < 0:
+            raise ValueError("ScalarAMG.level_matrix: no such level or matrix")
+        rows = self.describe()[level]["rows"]
+        ptr = np.zeros(rows + 1, dtype=np.int64)
+        col, vals = np.zeros(max(nnz, 1), dtype=np.int32), np.zeros(max(nnz, 1), dtype=np.float64)
+        if L.fcg_samg_level_matrix(self._h, level, which, _vp(ptr), _vp(col), _vp(vals), nnz) != nnz:
+            raise RuntimeError("ScalarAMG.level_matrix: no numeric setup yet, or the copy failed")
+        return ptr, col[:nnz], vals[:nnz]
+
+    def setup(self, Ktt):
+        """Numeric setup for K_TT with its Dirichlet rows applied (fcg_samg_setup); the tensor is
+        read in place by apply / solve until the next setup."""
+        rc = fcg.lib().fcg_samg_setup(self._h, _vp(Ktt), self._stream())
+        if rc != 0:
+            self._fail(rc)
+        self.setup_ms.append(fcg.lib().fcg_samg_setup_ms(self._h, -1))
+
+    def apply(self, Ktt, r, z):
+        """z = one V-cycle of r (asynchronous)."""
+        rc = fcg.lib().fcg_samg_apply(self._h, _vp(Ktt), _vp(r), _vp(z), self._stream())
+        if rc != 0:
+            self._fail(rc)
+
+    def solve(self, Ktt, b, x, rtol, max_iter=1000, setup=True):
+        """K_TT x = b from x = 0 by flexible CG with one V-cycle per step -> (steps, true relative
+        residual); setup=False iterates on the last setup."""
+        if setup:
+            self.setup(Ktt)
+        it, rel = ctypes.c_int(0), ctypes.c_double(0.0)
+        rc = fcg.lib().fcg_samg_solve(self._h, _vp(Ktt), _vp(b), _vp(x), float(rtol), int(max_iter),
+                                      ctypes.byref(it), ctypes.byref(rel), self._stream())
+        if rc != 0:
+            self._fail(rc)
+        return it.value, rel.value

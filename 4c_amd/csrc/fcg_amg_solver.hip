@@ -21,6 +21,7 @@
 #include <string>
 #include <vector>
 
+#include "fcg_amg_shared.hpp"
 #include "fcg_internal.hpp"
 #include "fourc_gpu.h"
 
@@ -28,7 +29,6 @@ namespace fcg_amgs {
 
 constexpr int kBlock = 256;
 constexpr int kMaxPartials = 1024;
-constexpr int64_t kDenseMax = 4096;  // largest coarsest level inverted densely (2 x 134 MB)
 inline unsigned blocks_for(int64_t n) { return unsigned((n + kBlock - 1) / kBlock); }
 inline unsigned capped(int64_t n) { return unsigned(std::max<int64_t>(1, std::min<int64_t>(kMaxPartials, (n + kBlock - 1) / kBlock))); }
 
@@ -734,7 +734,13 @@ void estimate_lmax(const Ops& o)
     hipLaunchKernelGGL(axpby_kernel, dim3(blocks_for(n)), dim3(kBlock), 0, o.s, 1.0, z, rzn / rz, p, n);
     rz = rzn;
   }
-  // largest eigenvalue of the Lanczos tridiagonal (bisection on the Sturm sequence)
+  o.lmax() = lanczos_lmax(al, be);
+}
+
+// largest eigenvalue of the Lanczos tridiagonal (bisection on the Sturm sequence); shared with the
+// scalar AMG of K_TT (fcg_amg_shared.hpp)
+double lanczos_lmax(const std::vector<double>& al, const std::vector<double>& be)
+{
   const int k = int(al.size());
   std::vector<double> a(static_cast<size_t>(k)), e(static_cast<size_t>(k), 0.0);
   for (int i = 0; i < k; ++i)
@@ -763,7 +769,7 @@ void estimate_lmax(const Ops& o)
     if (count_below(mid) >= k) hi = mid;
     else lo = mid;
   }
-  o.lmax() = hi;
+  return hi;
 }
 
 void cheb(const fcg_amg* hc, const Ops& o, const double* b, double* x, bool x_zero)
@@ -808,8 +814,7 @@ void coarse_solve(fcg_amg* h, const Ops& o, const double* b, double* x)
   const int64_t n = o.n();
   if (h->cinv && h->cn == n)
   {
-    hipLaunchKernelGGL(dense_mv_kernel, dim3(unsigned((n + kBlock / 64 - 1) / (kBlock / 64))), dim3(kBlock), 0,
-        o.s, h->cinv, b, x, n);
+    dense_mv(h->cinv, b, x, n, o.s);
     ck(hipGetLastError(), "dense_mv_kernel");
     return;
   }
@@ -954,6 +959,30 @@ void galerkin_from(fcg_amg* h, size_t l0, const double* K, hipStream_t s)
   coarse_factor(h, s);
 }
 
+// the dense coarsest level's launches, shared with the scalar AMG of K_TT (fcg_amg_shared.hpp)
+int64_t dense_inverse_work(int64_t n) { return 2 * kGJ * n + kGJ * kGJ; }
+
+int dense_inverse(double* const buf[2], double* work, int64_t n, int32_t* d_flag, hipStream_t s)
+{
+  double *Pinv = work, *W = Pinv + kGJ * kGJ, *C = W + kGJ * n;
+  const int64_t steps = (n + kGJ - 1) / kGJ;
+  for (int64_t t = 0; t < steps; ++t)
+  {
+    const double* src = buf[t & 1];
+    hipLaunchKernelGGL(gj_panel_kernel, dim3(blocks_for(n)), dim3(kBlock), 0, s, src, n, t * kGJ, Pinv, W, C,
+        d_flag);
+    hipLaunchKernelGGL(gj_update_kernel, dim3(blocks_for(n), unsigned(n)), dim3(kBlock), 0, s, src,
+        buf[(t + 1) & 1], n, t * kGJ, Pinv, W, C);
+  }
+  return int(steps & 1);
+}
+
+void dense_mv(const double* D, const double* x, double* y, int64_t n, hipStream_t s)
+{
+  hipLaunchKernelGGL(dense_mv_kernel, dim3(unsigned((n + kBlock / 64 - 1) / (kBlock / 64))), dim3(kBlock), 0, s,
+      D, x, y, n);
+}
+
 bool env_off(const char* name)
 {
   const char* v = std::getenv(name);
@@ -973,28 +1002,19 @@ void coarse_factor(fcg_amg* h, hipStream_t s)
   {
     h->cbuf[0] = dalloc<double>(h, n * n);
     h->cbuf[1] = dalloc<double>(h, n * n);
-    h->cwork = dalloc<double>(h, 2 * kGJ * n + kGJ * kGJ);
+    h->cwork = dalloc<double>(h, dense_inverse_work(n));
     h->cn = n;
   }
-  double *Pinv = h->cwork, *W = Pinv + kGJ * kGJ, *C = W + kGJ * n;
   ck(hipMemsetAsync(h->cbuf[0], 0, sizeof(double) * size_t(n * n), s), "memset");
   ck(hipMemsetAsync(h->flag, 0, sizeof(int32_t), s), "memset");
   hipLaunchKernelGGL(bsr6_dense_kernel, dim3(blocks_for(A.n * 36)), dim3(kBlock), 0, s, A.n, A.ptr, A.col,
       A.vals, h->cbuf[0]);
-  const int64_t steps = (n + kGJ - 1) / kGJ;
-  for (int64_t t = 0; t < steps; ++t)
-  {
-    const double* src = h->cbuf[t & 1];
-    hipLaunchKernelGGL(gj_panel_kernel, dim3(blocks_for(n)), dim3(kBlock), 0, s, src, n, t * kGJ, Pinv, W, C,
-        h->flag);
-    hipLaunchKernelGGL(gj_update_kernel, dim3(blocks_for(n), unsigned(n)), dim3(kBlock), 0, s, src,
-        h->cbuf[(t + 1) & 1], n, t * kGJ, Pinv, W, C);
-  }
+  const int inv = dense_inverse(h->cbuf, h->cwork, n, h->flag, s);
   ck(hipGetLastError(), "gj_update_kernel");
   int32_t bad = 0;
   ck(hipMemcpyAsync(&bad, h->flag, sizeof(bad), hipMemcpyDeviceToHost, s), "hipMemcpyAsync");
   ck(hipStreamSynchronize(s), "hipStreamSynchronize");
-  if (!bad) h->cinv = h->cbuf[steps & 1];
+  if (!bad) h->cinv = h->cbuf[inv];
 }
 
 // flexible CG (Polak-Ribiere) preconditioned by one V-cycle; one host read per iteration

@@ -57,3 +57,7 @@ struct fcg_tsi_ctx {
   std::string last_error;
   int64_t device_bytes = 0;
 };
+
+// the thermo context a scalar AMG handle was created on (fcg_samg.hip)
+struct fcg_samg;
+extern "C" const fcg_tsi_ctx* fcg_samg_context(const fcg_samg* h);

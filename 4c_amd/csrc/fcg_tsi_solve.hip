@@ -143,6 +143,32 @@ __global__ __launch_bounds__(kBlock) void tsi_thermal_precond_kernel(const int64
   if (t < nn && lane == 0) zT[t] = dtt[t] * (rT[t] - a);
 }
 
+// w_T = r_T - K_TS z_S in one pass over K_TS: the right-hand side of the thermal V-cycle under the
+// block Gauss-Seidel preconditioner (fcg_tsi_gmres_solve_amg with amg_t)
+template <int LPN>
+__global__ __launch_bounds__(kBlock) void tsi_thermal_rhs_kernel(const int64_t* __restrict__ rp_tt,
+    const int32_t* __restrict__ col_tt, const double* __restrict__ Kts, const double* __restrict__ rT,
+    const double* __restrict__ zS, double* __restrict__ wT, int64_t nn)
+{
+  const int lane = threadIdx.x % LPN;
+  const int64_t t = (int64_t(blockIdx.x) * kBlock + threadIdx.x) / LPN;
+  double a = 0.0;
+  if (t < nn)
+  {
+    const int64_t b = rp_tt[t];
+    const int l = int(rp_tt[t + 1] - b);
+    const double* ts = Kts + 3 * b;
+    for (int k = lane; k < l; k += LPN)
+    {
+      const int64_t c = col_tt[b + k];
+      a += ts[3 * k] * zS[3 * c] + ts[3 * k + 1] * zS[3 * c + 1] + ts[3 * k + 2] * zS[3 * c + 2];
+    }
+  }
+#pragma unroll
+  for (int o = LPN / 2; o >= 1; o >>= 1) a += __shfl_xor(a, o, LPN);
+  if (t < nn && lane == 0) wT[t] = rT[t] - a;
+}
+
 // dtt[t] = 1 / K_TT(t, t); a missing, zero or non-finite diagonal entry sets the flag
 __global__ __launch_bounds__(kBlock) void tsi_dtt_kernel(const int64_t* __restrict__ rp_tt,
     const int32_t* __restrict__ col_tt, const double* __restrict__ Ktt, double* __restrict__ dtt,
@@ -332,6 +358,8 @@ struct TsiOps : KrylovOps {
   const double *Kss, *Kst, *Kts, *Ktt;
   const double* dinv;  // nodal block Jacobi of K_SS (amg NULL)
   const double* dtt;   // 1 / diag K_TT
+  fcg_samg* amg_t = nullptr;  // the thermal V-cycle in place of dtt
+  double* wT = nullptr;       // its right-hand side under bgs
   int bgs;
   int apply(const double* x, double* y, hipStream_t s) override
   {
@@ -372,6 +400,23 @@ struct TsiOps : KrylovOps {
         error = sctx->last_error;
         return rc;
       }
+    }
+    if (amg_t)
+    {
+      const double* rhs = r + ns;
+      if (bgs)
+      {
+        if (d.npe == 27)
+          hipLaunchKernelGGL(tsi_thermal_rhs_kernel<64>, dim3(blocks_for(nn * 64)), dim3(kBlock), 0, s,
+              d.rowptr_tt, d.col_tt, Kts, r + ns, z, wT, nn);
+        else
+          hipLaunchKernelGGL(tsi_thermal_rhs_kernel<16>, dim3(blocks_for(nn * 16)), dim3(kBlock), 0, s,
+              d.rowptr_tt, d.col_tt, Kts, r + ns, z, wT, nn);
+        rhs = wT;
+      }
+      const int rc = fcg_samg_apply(amg_t, Ktt, rhs, z + ns, s);
+      if (rc != FCG_OK) error = fcg_samg_last_error(amg_t);
+      return rc;
     }
     if (d.npe == 27)
       hipLaunchKernelGGL(tsi_thermal_precond_kernel<64>, dim3(blocks_for(nn * 64)), dim3(kBlock), 0, s,
@@ -467,6 +512,15 @@ int fcg_tsi_gmres_solve(fcg_ctx* sctx, fcg_tsi_ctx* tctx, fcg_amg* amg_s, const 
     const double* d_bt, double* d_xs, double* d_xt, const fcg_gmres_options* opt, int* iterations,
     double* rel_residual, void* stream)
 {
+  return fcg_tsi_gmres_solve_amg(sctx, tctx, amg_s, nullptr, d_Kss, d_Kst, d_Kts, d_Ktt, d_bs, d_bt, d_xs,
+      d_xt, opt, iterations, rel_residual, stream);
+}
+
+int fcg_tsi_gmres_solve_amg(fcg_ctx* sctx, fcg_tsi_ctx* tctx, fcg_amg* amg_s, fcg_samg* amg_t,
+    const double* d_Kss, const double* d_Kst, const double* d_Kts, const double* d_Ktt,
+    const double* d_bs, const double* d_bt, double* d_xs, double* d_xt, const fcg_gmres_options* opt,
+    int* iterations, double* rel_residual, void* stream)
+{
   if (!tctx) return FCG_ERR_ARG;
   if (iterations) *iterations = 0;
   if (rel_residual) *rel_residual = 0.0;
@@ -480,6 +534,11 @@ int fcg_tsi_gmres_solve(fcg_ctx* sctx, fcg_tsi_ctx* tctx, fcg_amg* amg_s, const 
                        "and precond be 0 or 1";
     return FCG_ERR_ARG;
   }
+  if (amg_t && fcg_samg_context(amg_t) != tctx)
+  {
+    tctx->last_error = "fcg_tsi_gmres_solve: the thermal AMG was created on another thermo context";
+    return FCG_ERR_ARG;
+  }
   fcg::TsiDevice& d = tctx->d;
   const int64_t ns = d.n_rows_s, nn = d.n_rows_t, n = ns + nn;
   if (n == 0) return FCG_OK;
@@ -490,8 +549,9 @@ int fcg_tsi_gmres_solve(fcg_ctx* sctx, fcg_tsi_ctx* tctx, fcg_amg* amg_s, const 
   }
   // work space: the core's, then stacked b and x, the nodal block inverses of K_SS and 1 / diag K_TT
   const int64_t core = fcg::krylov_work_doubles(n, opt->restart);
-  hipError_t he = fcg::krylov_reserve(&d.krylov_work, &d.krylov_doubles, core + 2 * n + 3 * ns + nn,
-      &tctx->device_bytes);
+  // (with amg_t one more thermal vector, the V-cycle's right-hand side)
+  hipError_t he = fcg::krylov_reserve(&d.krylov_work, &d.krylov_doubles,
+      core + 2 * n + 3 * ns + nn + (amg_t ? nn : 0), &tctx->device_bytes);
   if (he != hipSuccess)
   {
     tctx->last_error = std::string("fcg_tsi_gmres_solve: work space: ") + hipGetErrorString(he);
@@ -539,6 +599,8 @@ int fcg_tsi_gmres_solve(fcg_ctx* sctx, fcg_tsi_ctx* tctx, fcg_amg* amg_s, const 
   ops.Ktt = d_Ktt;
   ops.dinv = dinv;
   ops.dtt = dtt;
+  ops.amg_t = amg_t;
+  ops.wT = dtt + nn;
   ops.bgs = opt->precond;
   std::string err;
   const int rc = fcg::fgmres(ops, n, b, x, opt->restart, opt->max_iter, opt->rtol, d.krylov_work, flag,

@@ -168,7 +168,11 @@ EXPORTS = ["fcg_create", "fcg_destroy", "fcg_last_error", "fcg_evaluate", "fcg_e
            "fcg_centrdiff_step", "fcg_stable_dt",
            "fcg_gmres_default_options", "fcg_gmres_solve", "fcg_gmres_set_timing",
            "fcg_gmres_get_timing", "fcg_gmres_orthogonalize_work", "fcg_gmres_orthogonalize",
-           "fcg_tsi_block_apply", "fcg_tsi_dirichlet_apply", "fcg_tsi_gmres_solve"]
+           "fcg_tsi_block_apply", "fcg_tsi_dirichlet_apply", "fcg_tsi_gmres_solve",
+           "fcg_samg_default_options", "fcg_samg_create", "fcg_samg_setup", "fcg_samg_apply",
+           "fcg_samg_solve", "fcg_samg_levels", "fcg_samg_level_info", "fcg_samg_level_matrix",
+           "fcg_samg_last_error", "fcg_samg_destroy", "fcg_samg_setup_ms", "fcg_tsi_gmres_solve_amg", "fcg_scsr_spmv",
+           "fcg_scsr_chebyshev_step"]
 
 _lib = None
 FUNCT_FN = ctypes.CFUNCTYPE(ctypes.c_double, ctypes.c_int, _dp, ctypes.c_double, ctypes.c_void_p)
@@ -349,6 +353,26 @@ def lib():
     L.fcg_tsi_dirichlet_apply.argtypes = [vp, i64, vp, i64, vp, vp, vp, vp, vp, vp]
     L.fcg_tsi_gmres_solve.argtypes = [vp] * 11 + [ctypes.POINTER(FcgGmresOptions),
                                                   ctypes.POINTER(c_int), _dp, vp]
+    L.fcg_samg_default_options.argtypes = [ctypes.POINTER(FcgAmgOptions)]
+    L.fcg_samg_default_options.restype = None
+    L.fcg_samg_create.argtypes = [vp, vp, vp, i64, vp, ctypes.POINTER(FcgAmgOptions), ctypes.POINTER(vp)]
+    L.fcg_samg_setup.argtypes = [vp, vp, vp]
+    L.fcg_samg_apply.argtypes = [vp, vp, vp, vp, vp]
+    L.fcg_samg_solve.argtypes = [vp, vp, vp, vp, c_dbl, c_int, ctypes.POINTER(c_int), _dp, vp]
+    L.fcg_samg_levels.argtypes = [vp]
+    L.fcg_samg_level_info.argtypes = [vp, c_int, _i64p, _i64p, _dp]
+    L.fcg_samg_level_matrix.argtypes = [vp, c_int, c_int, vp, vp, vp, i64]
+    L.fcg_samg_level_matrix.restype = i64
+    L.fcg_samg_last_error.argtypes = [vp]
+    L.fcg_samg_last_error.restype = ctypes.c_char_p
+    L.fcg_samg_destroy.argtypes = [vp]
+    L.fcg_samg_setup_ms.argtypes = [vp, c_int]
+    L.fcg_samg_setup_ms.restype = c_dbl
+    L.fcg_tsi_gmres_solve_amg.argtypes = [vp] * 12 + [ctypes.POINTER(FcgGmresOptions),
+                                                      ctypes.POINTER(c_int), _dp, vp]
+    L.fcg_scsr_spmv.argtypes = [c_int, i64, i64, vp, vp, vp, vp, vp, vp, c_dbl, c_int, vp]
+    L.fcg_scsr_chebyshev_step.argtypes = [c_int, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, c_dbl,
+                                          c_dbl, c_int, vp]
     _lib = L
     return L
 
@@ -1243,18 +1267,22 @@ class TsiEvaluator:
     PRECOND = {"diag": 0, "bgs": 1, 0: 0, 1: 1}
 
     def gmres_solve(self, struct_ev, Kss, Kst, Kts, Ktt, bs, bt, xs, xt, rtol=1e-10,
-                    max_iter=10000, restart=50, precond="bgs", amg=None, stream=None):
+                    max_iter=10000, restart=50, precond="bgs", amg=None, stream=None, amg_t=None):
         """fcg_tsi_gmres_solve: the monolithic system by restarted flexible GMRES on [x_S; x_T]
         from x = 0.  precond: "diag" (block diagonal) or "bgs" (block Gauss-Seidel); the
         structural block is the nodal block Jacobi of K_SS or one cycle of `amg` (an
-        amg.NativeAMG set up on K_SS), the thermal one the diagonal of K_TT.  Returns (inner steps
+        amg.NativeAMG set up on K_SS), the thermal one the diagonal of K_TT or one cycle of `amg_t`
+        (an amg.ScalarAMG set up on this K_TT; fcg_tsi_gmres_solve_amg).  Returns (inner steps
         taken, true relative residual of the stacked system)."""
         opt = gmres_options(restart, max_iter, rtol, self.PRECOND[precond])
         it, rr = ctypes.c_int(0), ctypes.c_double(0.0)
-        rc = lib().fcg_tsi_gmres_solve(struct_ev._h, self._h, amg._h if amg is not None else None,
-                                       *[_tensor_ptr(a) for a in (Kss, Kst, Kts, Ktt, bs, bt, xs, xt)],
-                                       ctypes.byref(opt), ctypes.byref(it), ctypes.byref(rr),
-                                       _torch_stream(stream, self.device))
+        blocks = [_tensor_ptr(a) for a in (Kss, Kst, Kts, Ktt, bs, bt, xs, xt)]
+        tail = (ctypes.byref(opt), ctypes.byref(it), ctypes.byref(rr), _torch_stream(stream, self.device))
+        hs = amg._h if amg is not None else None
+        if amg_t is not None:
+            rc = lib().fcg_tsi_gmres_solve_amg(struct_ev._h, self._h, hs, amg_t._h, *blocks, *tail)
+        else:
+            rc = lib().fcg_tsi_gmres_solve(struct_ev._h, self._h, hs, *blocks, *tail)
         if rc != 0:
             self._fail(rc)
         return it.value, rr.value

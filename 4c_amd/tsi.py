@@ -22,7 +22,8 @@ class TsiMonolithic:
     dbc_s / dbc_t: homogeneous Dirichlet row LIDs of the two fields.  fused: one
     fcg_tsi_evaluate_fused per iteration (True), two evaluates (False), or fused when the contexts
     qualify (None).  precond: "bgs" or "diag"; amg: an amg.NativeAMG of struct_ev for the
-    structural block (set up on every K_SS), None: nodal block Jacobi.
+    structural block (set up on every K_SS), None: nodal block Jacobi; amg_t: an amg.ScalarAMG of
+    tsi_ev for the thermal block (set up on every K_TT), None: the diagonal of K_TT.
 
     step() advances one time step, run(nstep) several; `history` holds per step the Newton
     iterations and per solve the GMRES iterations and relative residual.  Raises RuntimeError when
@@ -30,7 +31,7 @@ class TsiMonolithic:
 
     def __init__(self, struct_ev, tsi_ev, dt, fext_s, fext_t, dbc_s, dbc_t, T_init=None, fused=None,
                  tol_inc=1e-13, max_iter=30, lin_rtol=1e-10, restart=50, lin_max_iter=2000,
-                 precond="bgs", amg=None):
+                 precond="bgs", amg=None, amg_t=None):
         self.sev, self.tev, self.dt = struct_ev, tsi_ev, float(dt)
         self.dev = torch.device("cuda", struct_ev.device)
         g = tsi_ev.graph
@@ -44,6 +45,9 @@ class TsiMonolithic:
         self.precond, self.amg = precond, amg
         if amg is not None:
             amg.check_dirichlet(self.dbc_s.cpu().numpy())
+        self.amg_t = amg_t
+        if amg_t is not None:
+            amg_t.check_dirichlet(self.dbc_t.cpu().numpy())
         z = lambda n: torch.zeros(int(n), dtype=torch.float64, device=self.dev)
         self.d, self.T = z(self.ns), z(self.nt)
         if T_init is not None:
@@ -95,10 +99,12 @@ class TsiMonolithic:
             self.tev.dirichlet_apply(self.dbc_s, self.dbc_t, self.Kst, self.Kts, self.Ktt, self.fT)
             if self.amg is not None:
                 self.amg.setup(self.Kss)
+            if self.amg_t is not None:
+                self.amg_t.setup(self.Ktt)
             n, rel = self.tev.gmres_solve(self.sev, self.Kss, self.Kst, self.Kts, self.Ktt, self.fs,
                                           self.fT, self.dxs, self.dxt, rtol=self.lin_rtol,
                                           max_iter=self.lin_max_iter, restart=self.restart,
-                                          precond=self.precond, amg=self.amg)
+                                          precond=self.precond, amg=self.amg, amg_t=self.amg_t)
             rec["gmres_iterations"].append(n)
             rec["gmres_rel_residual"].append(rel)
             if not rel <= self.lin_rtol:

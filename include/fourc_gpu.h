@@ -779,6 +779,83 @@ int fcg_tsi_gmres_solve(fcg_ctx* sctx, fcg_tsi_ctx* tctx, fcg_amg* amg_s_or_null
     const double* d_bs, const double* d_bt, double* d_xs, double* d_xt,
     const fcg_gmres_options* opt, int* iterations, double* rel_residual, void* stream);
 
+/*
+ * Scalar smoothed-aggregation AMG of K_TT (fcg_samg_plan.cpp, fcg_samg.hip): the multigrid of the
+ * thermal block, one DOF per node, the constant as near-null space -- what MueLu builds for the
+ * thermal field of 4C's TSI block preconditioners, and a solver for a conduction problem on its
+ * own.  Two stages as fcg_amg: a host plan at create, a numeric setup per matrix.
+ *
+ * fcg_samg_create: a single-rank thermo context with node-consistent numbering (n_cols_t =
+ * n_rows_t, else FCG_ERR_ARG), its k_TT node graph on the host (int64 rowptr_tt, int32 col_tt,
+ * columns ascending) and the thermal Dirichlet rows, which join no aggregate: their prolongator
+ * rows stay empty (a row outside the map: FCG_ERR_ARG).  opt as fcg_amg_options (coarse_max_iter
+ * and coarse_rtol are not used: the coarsest level is always inverted densely, so a hierarchy that
+ * ends above 4096 rows is refused with FCG_ERR_ARG); NULL takes fcg_samg_default_options, the
+ * structural defaults with coarse_max = 300 rows (the structural 3000 DOFs are 500 coarse nodes of
+ * six DOFs; here a row is a node).  The tentative prolongator of node i is 1 / sqrt |agg(i)| on
+ * level 0 (B_i / |B_agg|_2 with the level's near-null-space vector B below), the coarse near-null
+ * space sqrt |agg|.  Errors of create are reported through fcg_tsi_last_error of the context;
+ * device memory is counted in the context's device_bytes.  Destroy the handle before the context.
+ *
+ * fcg_samg_setup: the numeric setup for d_Ktt (K_TT with its Dirichlet rows applied), read in
+ * place as level 0 -- no copy is kept, so the same buffer is passed to apply / solve and must stay
+ * unchanged until the next setup.  Per level: 1 / diag (a zero, missing or non-finite entry:
+ * FCG_ERR_SINGULAR), lambda_max(D^-1 A) by a 10-step Lanczos, P = T - (omega / lambda_max) D^-1
+ * (A T), A P and A_c = P^T (A P) from product plans, one thread per entry; the coarsest level's
+ * dense inverse (a pivot <= 0: FCG_ERR_SINGULAR).  Blocking.
+ * fcg_samg_apply: one V-cycle z = M r from z = 0: nu Chebyshev degrees before and after (each one
+ * fused kernel: residual, Jacobi scaling, update), the dense coarsest inverse.  Asynchronous on
+ * `stream`; before any setup FCG_ERR_ARG.
+ * fcg_samg_solve: flexible CG from x = 0 with one V-cycle per step to |r| <= rtol |b|;
+ * rel_residual is the true residual at return; FCG_ERR_SINGULAR when the cycle turns indefinite.
+ * With unit Dirichlet rows and b = 0 on them x comes back exactly 0.0 there.  Blocking.
+ * Every sum runs in a fixed order, no atomics on doubles: two setups, applies or solves give the
+ * same bits.
+ * fcg_samg_level_info: rows, non-zeros and the lambda_max estimate of level 0 .. levels - 1 (0 on
+ * the coarsest).  fcg_samg_level_matrix: a host copy of the level's CSR after the last setup,
+ * which = 0: A_l, 1: P_l (l < levels - 1); ptr[rows + 1], col / vals[capacity]; returns the
+ * non-zero count (ptr = col = vals = NULL: a size query), -1 on bad arguments.
+ * fcg_samg_setup_ms: host time of level's share of the last numeric setup (level l < levels - 1:
+ * the Lanczos estimate, P_l, A_l P_l and A_{l+1}; the coarsest level: its dense inverse), level
+ * -1: the whole setup.
+ *
+ * fcg_tsi_gmres_solve_amg: fcg_tsi_gmres_solve (= this call with amg_t NULL) with the thermal
+ * half of the preconditioner one V-cycle M_T of amg_t in place of D_TT^-1: precond 0
+ * z_T = M_T r_T, 1 z_T = M_T (r_T - K_TS z_S), the bracket formed in one pass over K_TS.  The
+ * caller has run fcg_samg_setup on this d_Ktt; a handle of another thermo context: FCG_ERR_ARG.
+ *
+ * fcg_scsr_spmv / fcg_scsr_chebyshev_step: the level kernels on any scalar CSR matrix in device
+ * memory (row_width: its longest row; it selects 4, 16 or 64 lanes per row).  spmv mode 0:
+ * y = alpha A x, 1: y += alpha A x, 2: y = b - A x.  chebyshev_step, with z = (b - A x) / a_ii
+ * and d_dinv = 1 / a_ii, the modes of fcg_chebyshev_step: 0: d = c_r z, 1: d = c_d d + c_r z,
+ * then x_out = x + d; 2: d = x_out = c_r b / a_ii (A and x are not read).  x_out must not be x.
+ */
+typedef struct fcg_samg fcg_samg;
+void fcg_samg_default_options(fcg_amg_options* opt);
+int fcg_samg_create(fcg_tsi_ctx* tctx, const int64_t* rowptr_tt, const int32_t* col_tt,
+    int64_t n_dbc, const int32_t* dbc_rows_t, const fcg_amg_options* opt, fcg_samg** out);
+int fcg_samg_setup(fcg_samg* amg, const double* d_Ktt, void* stream);
+int fcg_samg_apply(fcg_samg* amg, const double* d_Ktt, const double* d_r, double* d_z, void* stream);
+int fcg_samg_solve(fcg_samg* amg, const double* d_Ktt, const double* d_b, double* d_x, double rtol,
+    int max_iter, int* iterations, double* rel_residual, void* stream);
+int fcg_samg_levels(const fcg_samg* amg);
+int fcg_samg_level_info(const fcg_samg* amg, int level, int64_t* rows, int64_t* nnz, double* lmax);
+int64_t fcg_samg_level_matrix(const fcg_samg* amg, int level, int which, int64_t* ptr, int32_t* col,
+    double* vals, int64_t capacity);
+double fcg_samg_setup_ms(const fcg_samg* amg, int level);
+const char* fcg_samg_last_error(const fcg_samg* amg);
+int fcg_samg_destroy(fcg_samg* amg);
+int fcg_tsi_gmres_solve_amg(fcg_ctx* sctx, fcg_tsi_ctx* tctx, fcg_amg* amg_s_or_null,
+    fcg_samg* amg_t_or_null, const double* d_Kss, const double* d_Kst, const double* d_Kts,
+    const double* d_Ktt, const double* d_bs, const double* d_bt, double* d_xs, double* d_xt,
+    const fcg_gmres_options* opt, int* iterations, double* rel_residual, void* stream);
+int fcg_scsr_spmv(int device, int64_t n, int64_t row_width, const int64_t* d_ptr, const int32_t* d_col,
+    const double* d_vals, const double* d_x, const double* d_b, double* d_y, double alpha, int mode,
+    void* stream);
+int fcg_scsr_chebyshev_step(int device, int64_t n, int64_t row_width, const int64_t* d_ptr,
+    const int32_t* d_col, const double* d_vals, const double* d_dinv, const double* d_b,
+    const double* d_x, double* d_d, double* d_x_out, double c_d, double c_r, int mode, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Structured-box discretization builder: a restatement of 4C's GridGenerator
  * (src/core/io/src/4C_io_gridgenerator.cpp:41-392), node ownership of Rebalance::build_graph

@@ -14,8 +14,12 @@ Model, per inner step at the mean basis length j (mean of the steps' j over the 
 norm) against J + 1 basis vectors of the box's stacked length, the library's kernels
 (fcg_gmres_orthogonalize) and the same step in torch (h = V[:J+1] @ w, w.addmv_, twice, then the
 norm), alternated, medians of 30.
+--amg-s / --amg-t: amg.NativeAMG on K_SS / amg.ScalarAMG on K_TT in place of the Jacobi blocks
+(fcg_tsi_gmres_solve_amg); the line then also holds each AMG's levels, its numeric setup in ms
+(median of 3, host time around the blocking call) and the ms of one V-cycle (hipEvents, median
+of 20).  The byte model of the preconditioner covers the Jacobi blocks only.
 usage: tsi_solve_bench.py [--n N] [--precond bgs|diag] [--restart M] [--rtol R] [--max-iter K]
-                          [--orth-compare J]"""
+                          [--amg-s] [--amg-t] [--orth-compare J]"""
 import argparse
 import importlib
 import json
@@ -36,6 +40,8 @@ ap.add_argument("--restart", type=int, default=50)
 ap.add_argument("--rtol", type=float, default=1e-8)
 ap.add_argument("--max-iter", type=int, default=20000)
 ap.add_argument("--orth-compare", type=int, default=-1)
+ap.add_argument("--amg-s", action="store_true")
+ap.add_argument("--amg-t", action="store_true")
 a = ap.parse_args()
 if a.orth_compare >= 0:
     dev = torch.device("cuda:0")
@@ -107,9 +113,54 @@ ds, dt_ = torch.from_numpy(rows_s).to(dev), torch.from_numpy(rows_t).to(dev)
 ev.dirichlet_apply(ds, K["Kss"], fs)
 tev.dirichlet_apply(ds, dt_, K["Kst"], K["Kts"], K["Ktt"], fT)
 xs, xt = torch.zeros(ns, **f64), torch.zeros(nt, **f64)
+
+
+def cycle_ms(apply, K_, r, z):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    ms = []
+    for rep in range(23):
+        torch.cuda.synchronize()
+        e0.record()
+        apply(K_, r, z)
+        e1.record()
+        torch.cuda.synchronize()
+        if rep >= 3:
+            ms.append(e0.elapsed_time(e1))
+    return float(np.median(ms))
+
+
+def setup_ms(h, K_):
+    ms = []
+    for _ in range(3):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        h.setup(K_)
+        torch.cuda.synchronize()
+        ms.append(1e3 * (time.perf_counter() - t))
+    return float(np.median(ms))
+
+
+amg_s = amg_t = None
+amg_out = {}
+if a.amg_s or a.amg_t:
+    amg_mod = importlib.import_module("4c_amd.amg")
+if a.amg_s:
+    t = time.perf_counter()
+    amg_s = amg_mod.NativeAMG(m, ev, rows_s)
+    amg_out["amg_s"] = {"create_s": time.perf_counter() - t, "setup_ms": setup_ms(amg_s, K["Kss"]),
+                        "levels": [l["dofs"] for l in amg_s.describe()]}
+    apply_s = lambda K_, r, z: fcg.lib().fcg_amg_apply(amg_s._h, K_.data_ptr(), r.data_ptr(), z.data_ptr(),
+                                                       torch.cuda.current_stream(dev).cuda_stream)
+    amg_out["amg_s"]["vcycle_ms"] = cycle_ms(apply_s, K["Kss"], fs, torch.zeros_like(fs))
+if a.amg_t:
+    t = time.perf_counter()
+    amg_t = amg_mod.ScalarAMG(tev, rows_t)
+    amg_out["amg_t"] = {"create_s": time.perf_counter() - t, "setup_ms": setup_ms(amg_t, K["Ktt"]),
+                        "levels": [l["rows"] for l in amg_t.describe()]}
+    amg_out["amg_t"]["vcycle_ms"] = cycle_ms(amg_t.apply, K["Ktt"], fT, torch.zeros_like(fT))
 solve = lambda: tev.gmres_solve(ev, K["Kss"], K["Kst"], K["Kts"], K["Ktt"], fs, fT, xs, xt,
                                 rtol=a.rtol, max_iter=a.max_iter, restart=a.restart,
-                                precond=a.precond)
+                                precond=a.precond, amg=amg_s, amg_t=amg_t)
 solve()  # the first solve allocates the work space and verifies the graphs
 fcg.gmres_timing(True)
 torch.cuda.synchronize()
@@ -141,4 +192,5 @@ out = {"n": a.n, "unknowns": n, "precond": a.precond, "restart": a.restart, "rto
                      "precond": b_pre / 1e6 / max(1e-9, tm["precond_ms"] / steps),
                      "orth": b_orth / 1e6 / max(1e-9, tm["orth_ms"] / steps)},
        "hbm_copy_gbs": copy_gbs, "hbm_fill_gbs": fill_gbs}
+out.update(amg_out)
 print(json.dumps(out))
