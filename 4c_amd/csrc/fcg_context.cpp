@@ -47,7 +47,7 @@ void free_mesh(fcg::DeviceMesh& m)
   void* ptrs[] = {m.node_dof_row, m.node_dof_kcol, m.mass_ptr, m.mass_inc, m.mass_tab, m.mass_rho, m.mass_bad, m.stress_tab, m.stress_bad, m.stress_slot, m.explicit_work, m.ele_mat, m.apply_ye, m.apply_dof, m.diag_de, m.diag_dbc, m.gather_dummy, m.multi_ptr, m.rec_row0, m.rec_meta, m.rec_base, m.rec_ele, m.rec_a, m.rec_tmap, m.ele_orig, m.inc_ele, m.inc_a, m.asm_order, m.ele_x,
       m.ele_dof, m.ele_nodes, m.ele_gid, m.node_x, m.node_dof_col, m.inc_of, m.inc_ptr,
       m.rownode_row0, m.inc_pos, m.rowptr, m.scratch, m.err, m.elem_at, m.lat_x, m.lat_dof,
-      m.plane_rec,
+      m.plane_rec, m.reg_rec, m.reg_tile, m.reg_pos,
       m.tables, m.stamps, m.col_lid, m.diag_pos, m.pcg_work, m.krylov_work, m.col_ele, m.ele_ft, m.inc_row0, m.ele_gp,
       m.pen_ptr, m.ele_nb, m.h27_rows, m.h27_rslot0, m.h27_slot};
   for (void* p : ptrs)
@@ -288,6 +288,28 @@ void upload_structured(Uploader& U, const fcg_desc* d, const plan::NodeRows& N, 
   U.up(&m.lat_x, sp.lat_x);
   U.up(&m.lat_dof, sp.lat_dof);
   U.up(&m.plane_rec, sp.plane_rec);
+  // regular lattice tiles (classify_regular_tiles): the unchecked linear MODE-0 kernels take their
+  // closed-form row bookkeeping for the layers inside a tile's run.  A context that launches other
+  // kernels, or FCG_SWEEP_REGULAR=0 at fcg_create (A/B runs, tests), gets empty runs: today's path
+  const char* rg = std::getenv("FCG_SWEEP_REGULAR");
+  const bool regular = !(rg && rg[0] == '0') && d->kinematics == FCG_LINEAR && !m.sweep_defer;
+  m.layers_total = sp.layers_total;
+  m.reg_layers = regular ? sp.reg_layers : 0;
+  if (m.reg_layers > 0)
+  {
+    U.up(&m.reg_rec, sp.reg_rec);
+    U.up(&m.reg_tile, sp.reg_tile);
+  }
+  else
+  {
+    const std::vector<uint32_t> no_rec(fcg::REG_REC_WORDS, 0u);
+    const std::vector<int32_t> no_run(sp.reg_tile.size(), 0);
+    U.up(&m.reg_rec, no_rec);
+    U.up(&m.reg_tile, no_run);
+  }
+  int32_t pos32[32] = {};  // (indexed by the visit words' 5-bit block fields)
+  std::copy(sp.reg_pos, sp.reg_pos + 27, pos32);
+  U.up(&m.reg_pos, pos32, 32);
   // dN at the GPs [192] | dN at the nodes [192] | weights [8] | GP coordinates [24]
   std::vector<double> tab(8 * 8 * 3 * 2 + 8 + 24);
   double xi[81], w[27], xn[81];
@@ -869,6 +891,10 @@ int fcg_get_diagnostics(const fcg_ctx* ctx, uint64_t* out, int n)
   // slot 15 (no kernel counts there): the sweep kernels of this context
   v[15] = m.path != FCG_PATH_STRUCTURED ? FCG_SWEEP_KERNEL_NA
                                         : (m.sweep_checked ? FCG_SWEEP_KERNEL_CHECKED : FCG_SWEEP_KERNEL_UNCHECKED);
+  // slots 13, 14 (no kernel counts there either): the (tile, layer) pairs of the structured sweep
+  // that take the regular-tile path (none in a context that keeps the checked kernels), and all
+  v[13] = m.path == FCG_PATH_STRUCTURED && !m.sweep_checked ? uint64_t(m.reg_layers) : 0;
+  v[14] = m.path == FCG_PATH_STRUCTURED ? uint64_t(m.layers_total) : 0;
   for (int i = 0; i < n && i < 16; ++i) out[i] = v[i];
   return m.stamps ? 16 : 0;
 }

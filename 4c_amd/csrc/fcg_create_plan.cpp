@@ -16,6 +16,7 @@
 #include <climits>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <mutex>
 
 #include "fcg_shape.hpp"
@@ -530,7 +531,114 @@ bool build_structured_plan(const fcg_desc* d, const std::vector<int32_t>& rownod
       for (int q = 0; q < 27; ++q) np[27 * c + q] = P.nbr_pos[r * 27 + q];
     }
   });
+  classify_regular_tiles(P);
   return true;
+}
+
+// Regular lattice tiles.  On a lattice-numbered box nearly every plane record holds the same few
+// numbers: 81 entries per row, one pattern of neighbour positions, rows and bases in arithmetic
+// progression along a tile row.  The sweep's linear kernel then needs 12 words of a plane
+// instead of 288 and no record field in front of its K stores (fcg_sweep.hip, REG).
+void classify_regular_tiles(StructHost& P)
+{
+  const int64_t W = fcg::PLANE_REC_WORDS, NK = P.n[2];
+  const int64_t ntile = int64_t(P.tiles_y) * P.tiles_x;
+  P.reg_rec.assign(ntile * NK * REG_REC_WORDS, 0u);
+  P.reg_tile.assign(2 * ntile, 0);
+  std::fill(P.reg_pos, P.reg_pos + 27, 0);
+  P.reg_layers = 0;
+  P.layers_total = 0;
+  // the pattern: the most frequent one among the rows with all 27 neighbours (rows beside ghost
+  // columns, numbered behind the owned ones, have patterns of their own)
+  std::map<std::array<uint16_t, 27>, int64_t> seen;
+  const int64_t nrn = int64_t(P.nbr_pos.size()) / 27;
+  for (int64_t r = 0; r < nrn; ++r)
+  {
+    std::array<uint16_t, 27> a;
+    bool full = true;
+    for (int t = 0; t < 27; ++t)
+    {
+      a[t] = P.nbr_pos[r * 27 + t];
+      full = full && a[t] != 0xFFFF;
+    }
+    if (full) ++seen[a];
+  }
+  std::array<uint16_t, 27> pat{};
+  int64_t most = 0;
+  for (const auto& kv : seen)
+    if (kv.second > most)
+    {
+      most = kv.second;
+      pat = kv.first;
+    }
+  if (most > 0)
+    for (int t = 0; t < 27; ++t) P.reg_pos[t] = pat[t];
+  // planes
+  std::vector<uint8_t> plane_ok(ntile * NK, 0);
+  if (most > 0)
+    parallel_for(ntile * NK, [&](int64_t idx) {
+      const uint32_t* rec = P.plane_rec.data() + idx * W;
+      const uint16_t* np = reinterpret_cast<const uint16_t*>(rec + 64);
+      auto base_of = [&](int c) { return int64_t(uint64_t(rec[32 + 2 * c]) | (uint64_t(rec[32 + 2 * c + 1]) << 32)); };
+      for (int c = 0; c < 16; ++c)
+      {
+        if (rec[c] == 0xFFFFFFFFu || rec[16 + c] != 81u) return;
+        for (int t = 0; t < 27; ++t)
+          if (np[27 * c + t] != pat[t]) return;
+        const int c0 = c & ~3, cx = c & 3;
+        if (int64_t(rec[c]) != int64_t(rec[c0]) + 3 * cx || base_of(c) != base_of(c0) + 243 * cx) return;
+      }
+      uint32_t* cr = P.reg_rec.data() + idx * REG_REC_WORDS;
+      for (int y = 0; y < 4; ++y)
+      {
+        cr[y] = rec[4 * y];
+        cr[4 + 2 * y] = rec[32 + 8 * y];
+        cr[4 + 2 * y + 1] = rec[32 + 8 * y + 1];
+      }
+      cr[12] = 1u;
+      plane_ok[idx] = 1;
+    });
+  // runs of regular layers per tile; the elements of a layer: x, y one column around the tile
+  const int64_t EX = P.en[0], EY = P.en[1], EZ = P.en[2];
+  for (int64_t t = 0; t < ntile; ++t)
+  {
+    const int64_t tx = t % P.tiles_x, ty = t / P.tiles_x;
+    const int64_t x0 = int64_t(P.lo[0]) - P.elo[0] + 4 * tx, y0 = int64_t(P.lo[1]) - P.elo[1] + 4 * ty;
+    auto layer_ok = [&](int64_t k) {
+      if (k + 1 >= NK || !plane_ok[t * NK + k] || !plane_ok[t * NK + k + 1]) return false;
+      const int64_t ez = int64_t(P.lo[2]) - P.elo[2] + k;
+      if (ez < 0 || ez >= EZ) return false;
+      for (int64_t ey = y0 - 1; ey < y0 + 4; ++ey)
+        for (int64_t ex = x0 - 1; ex < x0 + 4; ++ex)
+          if (ex < 0 || ey < 0 || ex >= EX || ey >= EY || P.elem_at[(ez * EY + ey) * EX + ex] < 0) return false;
+      return true;
+    };
+    int64_t best_lo = 0, best_n = 0, run_lo = 0, run_n = 0;
+    for (int64_t k = 0; k < NK; ++k)
+    {
+      if (layer_ok(k))
+      {
+        if (run_n == 0) run_lo = k;
+        if (++run_n > best_n)
+        {
+          best_n = run_n;
+          best_lo = run_lo;
+        }
+      }
+      else
+        run_n = 0;
+    }
+    const int64_t lo = best_lo, hi = best_n > 0 ? best_lo + best_n + 1 : best_lo;
+    P.reg_tile[2 * t] = int32_t(lo);
+    P.reg_tile[2 * t + 1] = int32_t(hi);
+    // the sweep's segments: workgroup tz writes planes [kz0, kz1) and runs layers kz0 - 1 .. kz1 - 1
+    for (int64_t tz = 0; tz < P.tiles_z; ++tz)
+    {
+      const int64_t kz0 = int64_t(P.seg) * tz, kz1 = std::min<int64_t>(kz0 + P.seg, NK);
+      P.layers_total += kz1 - kz0 + 1;
+      P.reg_layers += std::max<int64_t>(0, std::min(hi, kz1) - 1 - std::max(lo, kz0));
+    }
+  }
 }
 
 // Colour-ordered direct assembly plan (hex27 on a verified lattice).  Element e at lattice

@@ -20,6 +20,8 @@ namespace fcg {
 // One record per (tile, node plane): row0[16] | rowlen[16] | rbase[16] (int64) | npos[16][27]
 // (uint16, column position of lattice neighbour t inside the node's rows, 0xFFFF = absent).
 constexpr int PLANE_REC_WORDS = 288;
+// Compact record of a regular (tile, node plane), see StructHost::reg_rec.
+constexpr int REG_REC_WORDS = 16;
 
 namespace create {
 
@@ -88,7 +90,22 @@ struct StructHost {
   std::vector<int32_t> lat_dof;     // column LID of the node's first DOF, -1 = none
   std::vector<uint32_t> plane_rec;  // [tiles_y][tiles_x][NK][PLANE_REC_WORDS]
   int64_t rows_unordered = 0;       // rows whose lower-plane neighbours are not their first columns
+  // Regular lattice tiles (classify_regular_tiles): a (tile, node plane) whose 16 columns are
+  // owned rows of 81 entries with the context's one neighbour-position pattern reg_pos, row0
+  // advancing by 3 and base by 243 along each of the tile's four y-rows.  Its compact record:
+  // row0 of the four y-rows [4] | their bases [4] (int64) | 1.  A plane that is not regular has
+  // an all-zero compact record.
+  std::vector<uint32_t> reg_rec;    // [tiles_y][tiles_x][NK][REG_REC_WORDS]
+  // per tile the longest run [lo, hi) of node planes (relative to the owned box) whose layers
+  // lo .. hi-2 are regular: planes L and L+1 regular and all 25 elements of the layer present
+  std::vector<int32_t> reg_tile;    // [tiles_y][tiles_x][2]
+  int32_t reg_pos[27] = {};         // the pattern (all zero when no row has 27 neighbours)
+  // (tile, layer) pairs the sweep's workgroups run: all, and those inside their tile's run and
+  // their segment's write range
+  int64_t reg_layers = 0, layers_total = 0;
 };
+// fills the reg_* members from the plan's tables (pure index arithmetic)
+void classify_regular_tiles(StructHost& P);
 bool detect_lattice_hex8(const fcg_desc* d, std::vector<int32_t>& ijk, std::vector<int32_t>& canon,
     std::string& why);
 bool build_structured_plan(const fcg_desc* d, const std::vector<int32_t>& rownodes,

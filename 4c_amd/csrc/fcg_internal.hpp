@@ -123,6 +123,12 @@ struct DeviceMesh {
   double* lat_x = nullptr;          // [EZ+1][EY+1][EX+1][3] node coordinates on the lattice
   int32_t* lat_dof = nullptr;       // [EZ+1][EY+1][EX+1] column LID of the node's first DOF or -1
   uint32_t* plane_rec = nullptr;    // [tiles_y][tiles_x][NK][PLANE_REC_WORDS] row bookkeeping
+  // regular lattice tiles (fcg_create_plan.hpp, classify_regular_tiles): compact records, the plane
+  // run of each tile (empty when the context does not use them) and the neighbour-position pattern
+  uint32_t* reg_rec = nullptr;      // [tiles_y][tiles_x][NK][REG_REC_WORDS]
+  int32_t* reg_tile = nullptr;      // [tiles_y][tiles_x][2]
+  int32_t* reg_pos = nullptr;       // [32], 27 used
+  int64_t reg_layers = 0, layers_total = 0;  // (tile, layer) pairs on the regular path / in all
   double* tables = nullptr;         // dN at GPs [192], dN at nodes [192], weights [8]
   unsigned long long* stamps = nullptr;  // diagnostic phase timers (FCG_STAMPS=1), else NULL
 

@@ -30,6 +30,8 @@
 // displacements) and plane record while the current layer computes.
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "fcg_hex8_element.hpp"
 #include "fcg_internal.hpp"
 #include "fcg_visit_table.h"
@@ -66,6 +68,10 @@ struct SweepArgs {
   const int32_t* lat_dof;    // [LZ][LY][LX] column LID of the first DOF, -1 = no node
   const int32_t* elem_at;    // [EZ][EY][EX] column element or -1
   const uint32_t* plane_rec; // [tiles_y][tiles_x][NK][PLANE_REC_WORDS]
+  // regular lattice tiles (REGK kernels): compact records, plane run per tile, position pattern
+  const uint32_t* reg_rec;   // [tiles_y][tiles_x][NK][REG_REC_WORDS]
+  const int32_t* reg_tile;   // [tiles_y][tiles_x][2]
+  const int32_t* reg_pos;    // [32], 27 used
   const double* tables;
   double* K;
   double* fint;
@@ -555,7 +561,13 @@ __device__ inline void block_k(const StVK& m, const double* acc, double* Kb)
 #pragma unroll
   for (int r = 0; r < 3; ++r)
 #pragma unroll
-    for (int q = 0; q < 3; ++q) Kb[3 * r + q] = lam * acc[3 * r + q] + mu * acc[3 * q + r];
+    for (int q = 0; q < 3; ++q)
+    {
+      // the contraction spelled out (fma(lam, G_rq, mu G_qr), what the compiler has always made of
+      // lam * G_rq + mu * G_qr here): left to the compiler, which of the two products is fused
+      // depends on the code around the inlined call, and the last bits of K with it
+      Kb[3 * r + q] = __builtin_fma(lam, acc[3 * r + q], mu * acc[3 * q + r]);
+    }
   if (KIN == 0)
   {
     const double tr = mu * (acc[0] + acc[4] + acc[8]);
@@ -625,6 +637,27 @@ __global__ __launch_bounds__(256, KIN ? 1 : FCG_SWEEP_WGS) void sweep_h8_kernel(
   const int kz1 = min(kz0 + A.seg_planes, A.K0 + A.NK);
   const uint32_t* prec_tile = A.plane_rec + (int64_t(ty) * A.tiles_x + tx) * A.NK * PLANE_REC_WORDS;
   const int64_t LX = A.EX + 1, LY = A.EY + 1;
+  // Regular layers (REGK: the unchecked linear MODE-0 kernels).  fcg_create has found, per tile,
+  // a run of node planes whose rows all have 81 entries, one pattern of neighbour positions and
+  // rows / bases in arithmetic progression along a tile row, with all 25 elements of every layer
+  // between them present (classify_regular_tiles).  The layers rlo <= L < rhi of this workgroup
+  // lie inside the run and the write range: their emits take pos from lane constants, len = 81
+  // as a literal and row0 / base from the four tile rows' words of the record, with no validity
+  // branch; their element ids are not loaded; and a plane both of whose layers are regular is
+  // loaded as its compact record (12 words instead of 288), put where the full record holds the
+  // same words.  All of it is workgroup-uniform (scalar compares).
+  constexpr bool REGK = MODE == 0 && KIN == 0 && !CHECKED;
+  int rlo = 0, rhi = 0;
+  const uint32_t* creg_tile = nullptr;
+  if constexpr (REGK)
+  {
+    const int64_t txy = int64_t(ty) * A.tiles_x + tx;
+    rlo = max(A.K0 + A.reg_tile[2 * txy], kz0);
+    rhi = min(A.K0 + A.reg_tile[2 * txy + 1], kz1) - 1;
+    creg_tile = A.reg_rec + txy * A.NK * REG_REC_WORDS;
+  }
+  auto reg_layer = [&](int L) -> bool { return REGK && L >= rlo && L < rhi; };
+  auto reg_plane = [&](int p) -> bool { return REGK && p > rlo && p < rhi; };  // layers p - 1 and p
 
   if (tid < 24) sh.gxi[tid / 3][tid % 3] = A.tables[392 + tid];
   if (tid < 8) sh.w8[tid] = A.tables[384 + tid];
@@ -641,6 +674,8 @@ __global__ __launch_bounds__(256, KIN ? 1 : FCG_SWEEP_WGS) void sweep_h8_kernel(
   const int ex = i0 - 1 + sx, ey = j0 - 1 + sy;
   const bool exy_in = a_lane && ex >= A.EX0 && ex < A.EX0 + A.EX && ey >= A.EY0 && ey < A.EY0 + A.EY;
   auto load_elem = [&](int lz) -> int {
+    // a regular layer holds all 25 elements, and REGK kernels use the id only as "present"
+    if (reg_layer(lz)) return a_lane ? 0 : -1;
     if (!exy_in || lz < A.EZ0 || lz >= A.EZ0 + A.EZ) return -1;
     return A.elem_at[(int64_t(lz - A.EZ0) * A.EY + (ey - A.EY0)) * A.EX + (ex - A.EX0)];
   };
@@ -687,19 +722,28 @@ __global__ __launch_bounds__(256, KIN ? 1 : FCG_SWEEP_WGS) void sweep_h8_kernel(
   auto load_rec = [&](int p, uint32_t* w) {
     const bool in = p >= kz0 && p < kz1;
     const uint32_t* src = prec_tile + int64_t(in ? p - A.K0 : 0) * PLANE_REC_WORDS;
+    // (a compact plane lies inside the write range) one load behind a selected address and
+    // predicate, as load_val: lanes 0..11 fetch the compact record's words, nobody a second word
+    const bool cp = reg_plane(p);
+    if (cp) src = creg_tile + int64_t(p - A.K0) * REG_REC_WORDS;
 #pragma unroll
     for (int k = 0; k < 2; ++k)
     {
       const int v = tid + 256 * k;
-      if (v < PLANE_REC_WORDS) w[k] = in ? src[v] : (v < PR_LEN ? 0xFFFFFFFFu : 0u);
+      if (v < PLANE_REC_WORDS) w[k] = (in && (!cp || v < 12)) ? src[v] : (v < PR_LEN ? 0xFFFFFFFFu : 0u);
     }
   };
   auto store_rec = [&](int p, const uint32_t* w) {
+    // compact word v: row0 of tile row v (v < 4), else half (v & 1) of tile row (v - 4) / 2's base,
+    // each at the place of the row's first column in the full record; the slot's other words are
+    // stale and not read (both layers of a compact plane take the regular emit)
+    const bool cp = reg_plane(p);
 #pragma unroll
     for (int k = 0; k < 2; ++k)
     {
       const int v = tid + 256 * k;
-      if (v < PLANE_REC_WORDS) sh.prec[ring(p)][v] = w[k];
+      const int at = cp ? (v < 4 ? PR_ROW0 + 4 * v : PR_BASE + 8 * (((v - 4) >> 1) & 3) + (v & 1)) : v;
+      if (v < PLANE_REC_WORDS && (!cp || v < 12)) sh.prec[ring(p)][at] = w[k];
     }
   };
 
@@ -707,6 +751,15 @@ __global__ __launch_bounds__(256, KIN ? 1 : FCG_SWEEP_WGS) void sweep_h8_kernel(
   const int c = tid >> 4, k = tid & 15;
   const int cx = c % TX, cy = c / TX;
   const uint32_t vis0 = kVisit[k][0], vis1 = kVisit[k][1];
+  // regular layers: entry offset of this lane's three blocks from the base of its tile row's
+  // first column (the pattern's position plus 243 per column), lane constants
+  int32_t rp_a = 0, rp_b = 0, rp_s = 0;  // first visit's block, second visit's, self block
+  if constexpr (REGK && WANT_K)
+  {
+    rp_a = A.reg_pos[(vis0 >> 16) & 31] + 243 * cx;
+    rp_b = A.reg_pos[(vis1 >> 16) & 31] + 243 * cx;
+    rp_s = A.reg_pos[(vis1 >> 11) & 31] + 243 * cx;
+  }
 
   // --- prologue: node planes kz0-1, kz0 and their records; prefetch plane kz0+1
 #pragma unroll
@@ -804,8 +857,12 @@ __global__ __launch_bounds__(256, KIN ? 1 : FCG_SWEEP_WGS) void sweep_h8_kernel(
     double fpart[NF];
 #pragma unroll
     for (int d = 0; d < NF; ++d) fpart[d] = 0.0;
-    if (WANT_K || KIN == 0)
+    // the visit stage, once per emit flavour: REG (a regular layer of a REGK kernel) takes the
+    // record-free emit described at rlo / rhi above, everything else the records
+    const bool regL = reg_layer(L);
+    auto visit_stage = [&](auto reg_c)
     {
+      constexpr bool REG = decltype(reg_c)::value;
       // finished block t of this lane's column (this layer's elements): hold it, or write it plus
       // the part held by lane k + 8 (same role, D side) since the previous layer.  TSI: Tv holds
       // the block's k_ST / k_TS / k_TT entries (tsi_block), treated the same way.
@@ -831,11 +888,23 @@ __global__ __launch_bounds__(256, KIN ? 1 : FCG_SWEEP_WGS) void sweep_h8_kernel(
       };
       auto emit_load = [&](int act, int t, EmitIn& in) {
         const uint32_t* rec = act == kActWriteL1 ? recL1 : recL;
-        in.row0 = WANT_K ? int32_t(rec[PR_ROW0 + c]) : -1;
-        in.pos = WANT_K ? reinterpret_cast<const uint16_t*>(rec + PR_NPOS)[27 * c + t] : 0;
-        in.base_lo = WANT_K ? rec[PR_BASE + 2 * c] : 0u;
-        in.base_hi = WANT_K ? rec[PR_BASE + 2 * c + 1] : 0u;
-        in.len32 = WANT_K ? int32_t(rec[PR_LEN + c]) : 0;
+        if constexpr (REG)
+        {
+          // the base of the tile row's first column: the one record field a regular emit reads
+          in.row0 = 0;
+          in.pos = 0;
+          in.len32 = 81;
+          in.base_lo = WANT_K ? rec[PR_BASE + 8 * cy] : 0u;
+          in.base_hi = WANT_K ? rec[PR_BASE + 8 * cy + 1] : 0u;
+        }
+        else
+        {
+          in.row0 = WANT_K ? int32_t(rec[PR_ROW0 + c]) : -1;
+          in.pos = WANT_K ? reinterpret_cast<const uint16_t*>(rec + PR_NPOS)[27 * c + t] : 0;
+          in.base_lo = WANT_K ? rec[PR_BASE + 2 * c] : 0u;
+          in.base_hi = WANT_K ? rec[PR_BASE + 2 * c + 1] : 0u;
+          in.len32 = WANT_K ? int32_t(rec[PR_LEN + c]) : 0;
+        }
         if (KIN == 0)
         {
           const int dx = t % 3 - 1, dy = (t / 3) % 3 - 1, dz = t / 9 - 1;
@@ -859,7 +928,8 @@ __global__ __launch_bounds__(256, KIN ? 1 : FCG_SWEEP_WGS) void sweep_h8_kernel(
           for (int i = 0; i < 9; ++i) in.held[i] = hr[i];
         }
       };
-      auto emit_finish = [&](int act, int t, const EmitIn& in, double* Kb, double* Tv) {
+      // rp: the block's entry offset in a regular layer (rp_a / rp_b / rp_s)
+      auto emit_finish = [&](int act, int t, const EmitIn& in, int32_t rp, double* Kb, double* Tv) {
         const bool to_l1 = act == kActWriteL1;
         const int32_t row0 = in.row0, len32 = in.len32;
         const uint32_t base_lo = in.base_lo, base_hi = in.base_hi;
@@ -870,7 +940,8 @@ __global__ __launch_bounds__(256, KIN ? 1 : FCG_SWEEP_WGS) void sweep_h8_kernel(
           const double u0 = in.u0, u1 = in.u1, u2 = in.u2;
           if (!TH)
 #pragma unroll
-            for (int r = 0; r < 3; ++r) fpart[r] += Kb[3 * r] * u0 + Kb[3 * r + 1] * u1 + Kb[3 * r + 2] * u2;
+            for (int r = 0; r < 3; ++r)  // (contraction spelled out as in block_k, the compiler's own so far)
+              fpart[r] += __builtin_fma(Kb[3 * r + 2], u2, __builtin_fma(Kb[3 * r], u0, Kb[3 * r + 1] * u1));
           if (TSI)
           {
             // f_S += k_ST (T - T_0) (partition of unity), f_T = k_TT T (exact for linear TSI)
@@ -961,14 +1032,16 @@ __global__ __launch_bounds__(256, KIN ? 1 : FCG_SWEEP_WGS) void sweep_h8_kernel(
             return;
           }
         }
-        if (!(to_l1 ? wl1 : wl) || row0 < 0 || pos == 0xFFFF) return;
+        // (a regular layer lies inside the write range, its rows are owned and hold all 27 blocks)
+        if constexpr (!REG)
+          if (!(to_l1 ? wl1 : wl) || row0 < 0 || pos == 0xFFFF) return;
         const int64_t base = int64_t(base_lo) | (int64_t(base_hi) << 32);
-        const int64_t len = len32;
+        const int64_t len = REG ? int64_t(81) : int64_t(len32);
 #ifdef FCG_PROBE_KL2
         // timing probe only (wrong results): the same stores, folded into 256 KB (L2-resident)
         double* dst = A.K + ((base + pos) & 0x7FFF);
 #else
-        double* dst = A.K + base + pos;
+        double* dst = A.K + base + (REG ? int64_t(rp) : int64_t(pos));
 #endif
 #ifdef FCG_PROBE_NOKSTORE
         // timing probe only (wrong results): no K stores
@@ -1063,11 +1136,11 @@ __global__ __launch_bounds__(256, KIN ? 1 : FCG_SWEEP_WGS) void sweep_h8_kernel(
             *d3 += Tv[6];
         }
       };
-      auto emit = [&](int act, int t, double* Kb, double* Tv) {
+      auto emit = [&](int act, int t, int32_t rp, double* Kb, double* Tv) {
         EmitIn in;
         emit_load(act, t, in);
         __asm__ volatile("" ::: "memory");
-        emit_finish(act, t, in, Kb, Tv);
+        emit_finish(act, t, in, rp, Kb, Tv);
       };
       double acc1[NACC], acc2[NACC];
 #pragma unroll
@@ -1131,7 +1204,7 @@ __global__ __launch_bounds__(256, KIN ? 1 : FCG_SWEEP_WGS) void sweep_h8_kernel(
             for (int i = 0; i < 9; ++i) Kb2[i] = Kb[i];
           }
           else
-            emit(int((w >> 21) & 7), int((w >> 16) & 31), Kb, Tv);
+            emit(int((w >> 21) & 7), int((w >> 16) & 31), v == 0 ? rp_a : rp_b, Kb, Tv);
         }
       }
       // acc1: the self block's two halves meet in lane r = 2 (order: qy = 1 half + qy = 0 half)
@@ -1170,14 +1243,26 @@ __global__ __launch_bounds__(256, KIN ? 1 : FCG_SWEEP_WGS) void sweep_h8_kernel(
           emit_load(act, t2, in2);
           emit_load(act, t1, in1);
           __asm__ volatile("" ::: "memory");
-          if (fl2) emit_finish(act, t2, in2, Kb2, Tv);
+          if (fl2) emit_finish(act, t2, in2, rp_b, Kb2, Tv);
           // (the second block's work stays behind the first's: interleaved, the two cost spills)
           __builtin_amdgcn_sched_barrier(0);
-          if (own) emit_finish(act, t1, in1, Kb, Tv);
+          if (own) emit_finish(act, t1, in1, rp_s, Kb, Tv);
         }
         else if (pair != kPairGive)
-          emit(int((vis1 >> 21) & 7), int((vis1 >> 11) & 31), Kb, Tv);
+          emit(int((vis1 >> 21) & 7), int((vis1 >> 11) & 31), rp_s, Kb, Tv);
       }
+    };
+    if (WANT_K || KIN == 0)
+    {
+      if constexpr (REGK)
+      {
+        if (regL)
+          visit_stage(std::true_type{});
+        else
+          visit_stage(std::false_type{});
+      }
+      else
+        visit_stage(std::false_type{});
     }
     // residual rows of the column: the 8 lanes of a side sum their parts by a butterfly (every
     // lane ends with the same bits); lane 8 keeps plane L+1's D-side part for the next layer, lane
@@ -1217,7 +1302,8 @@ __global__ __launch_bounds__(256, KIN ? 1 : FCG_SWEEP_WGS) void sweep_h8_kernel(
           f[2] += cc * (P[2] * t0 + P[5] * t1 + P[8] * t2);
         }
       }
-      const int32_t frow0 = int32_t(recL[PR_ROW0 + c]);  // read ahead of the butterfly
+      // read ahead of the butterfly (a regular layer: the tile row's first row0 plus 3 per column)
+      const int32_t frow0 = int32_t(recL[PR_ROW0 + (regL ? 4 * cy : c)]) + (regL ? 3 * cx : 0);
       double fp[NF];
 #pragma unroll
       for (int d = 0; d < NF; ++d)
@@ -1282,6 +1368,9 @@ SweepArgs sweep_args(const DeviceMesh& m, const double* d_u_col, double* d_K, do
   a.lat_dof = m.lat_dof;
   a.elem_at = m.elem_at;
   a.plane_rec = m.plane_rec;
+  a.reg_rec = m.reg_rec;
+  a.reg_tile = m.reg_tile;
+  a.reg_pos = m.reg_pos;
   a.tables = m.tables;
   a.K = d_K;
   a.fint = d_fint;

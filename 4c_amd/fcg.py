@@ -1066,6 +1066,16 @@ class Evaluator:
         lib().fcg_get_diagnostics(self._h, buf, 16)
         return self.SWEEP_KERNELS[int(buf[15])]
 
+    def sweep_regular_layers(self):
+        """(regular, total): the (tile, layer) pairs of the structured sweep that take the
+        regular-tile path -- closed-form row bookkeeping, decided at fcg_create -- and all of them
+        (slots 13, 14 of fcg_get_diagnostics).  regular is 0 for a context whose kernels keep
+        the plane records (TotLag, rows not in lattice order, the checked kernels) and with
+        FCG_SWEEP_REGULAR=0 at creation; (0, 0) on the other paths."""
+        buf = (ctypes.c_uint64 * 16)()
+        lib().fcg_get_diagnostics(self._h, buf, 16)
+        return int(buf[13]), int(buf[14])
+
     CREATE_PHASES = ("checks", "graph_device", "node_rows", "lattice_plans", "incidences",
                      "incidence_positions", "device_plans", "total")
 

@@ -233,7 +233,12 @@ int fcg_measure_hbm(int device, double* copy_gbs, double* write_gbs);
  * of fcg_create found no rejected element and no negative det J w (the reference coordinates do
  * not change during a context's life, so the evaluates need not look again),
  * FCG_SWEEP_KERNEL_CHECKED when it found one or FCG_SWEEP_CHECKED=1 was set at fcg_create,
- * FCG_SWEEP_KERNEL_NA on every other path. */
+ * FCG_SWEEP_KERNEL_NA on every other path.
+ * out[13], out[14] are no counters either and are always filled: the (tile, layer) pairs of the
+ * structured sweep that take the regular-tile path (closed-form row bookkeeping for tiles whose
+ * rows fcg_create found to be 81 entries long with one neighbour pattern and rows and bases in
+ * arithmetic progression; the unchecked linear kernels only, none with FCG_SWEEP_REGULAR=0 at
+ * fcg_create), and all pairs the sweep's workgroups run; both 0 on every other path. */
 #define FCG_SWEEP_KERNEL_NA 0
 #define FCG_SWEEP_KERNEL_CHECKED 1
 #define FCG_SWEEP_KERNEL_UNCHECKED 2
