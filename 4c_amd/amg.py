@@ -480,6 +480,46 @@ class NativeAMG:
             raise fcg.FcgError(rc, L.fcg_amg_last_error(self._h).decode())
         self.setup_ms.append(L.fcg_amg_setup_ms(self._h))
 
+    def apply(self, K, r, z):
+        """z = one V-cycle of r on the last setup (fcg_amg_apply; asynchronous, the caller's order
+        in and out)."""
+        L = fcg.lib()
+        s = ctypes.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
+        rc = L.fcg_amg_apply(self._h, _vp(K), _vp(r), _vp(z), s)
+        if rc != 0:
+            raise fcg.FcgError(rc, L.fcg_amg_last_error(self._h).decode())
+
+    def level_matrix(self, level, which):
+        """Host copies of the last setup (fcg_amg_level_matrix).  which 0 / 1 / 2: (ptr, col, vals)
+        of A_level, P_level, T_level in BSR, vals [blocks][br][bc]; 3: the smoother's block inverses
+        [n][b][b]; 4: the dense inverse of the coarsest level [n][n]."""
+        L = fcg.lib()
+        count = L.fcg_amg_level_matrix(self._h, level, which, None, None, None, 0)
+        if count < 0:
+            raise ValueError("NativeAMG.level_matrix: no such level or matrix")
+        info = self.describe()
+        br = 3 if level == 0 else _NM
+        n = info[level]["dofs"] // br
+        vals = np.full(max(count, 1), np.nan)
+        if which >= 3:
+            if L.fcg_amg_level_matrix(self._h, level, which, None, None, _vp(vals), count) != count:
+                raise RuntimeError("NativeAMG.level_matrix: no numeric setup yet, or the copy failed")
+            return vals[:count].reshape((n, br, br) if which == 3 else (n * br, n * br))
+        bc = br if which == 0 else _NM
+        nnzb = count // (br * bc)
+        ptr = np.full(n + 1, -1, dtype=np.int64)
+        col = np.full(max(nnzb, 1), -1, dtype=np.int32)
+        if L.fcg_amg_level_matrix(self._h, level, which, _vp(ptr), _vp(col), _vp(vals), count) != count:
+            raise RuntimeError("NativeAMG.level_matrix: no numeric setup yet, or the copy failed")
+        return ptr, col[:nnzb], vals[:count].reshape(nnzb, br, bc)
+
+    def order(self):
+        """new2old [n0 / 3]: the context's node of level 0's node p (fcg_amg_level_order; the
+        identity without the Morton reordering)."""
+        out = np.full(int(self.ev.info.n_rows) // 3, -1, dtype=np.int32)
+        _check(fcg.lib().fcg_amg_level_order(self._h, _vp(out)), "fcg_amg_level_order")
+        return out
+
     def solve(self, K, b, x, rtol, max_iter=1000, setup=True):
         """K x = b from x = 0; setup=False iterates on the last setup (a constant operator)."""
         L = fcg.lib()

@@ -23,6 +23,7 @@
 
 #include "fcg_amg_shared.hpp"
 #include "fcg_internal.hpp"
+#include "fcg_status.hpp"
 #include "fourc_gpu.h"
 
 namespace fcg_amgs {
@@ -2801,6 +2802,74 @@ int fcg_amg_stats(const fcg_amg* h, int* coarse_dense, int* graph_launches)
 }
 
 const char* fcg_amg_last_error(const fcg_amg* h) { return h ? h->last_error.c_str() : ""; }
+
+// Host copies of what the last fcg_amg_setup left on the device (tests rebuild the hierarchy and
+// the V-cycle from them): synchronises and copies, starts no kernel, changes nothing in the handle
+int64_t fcg_amg_level_matrix(const fcg_amg* h, int level, int which, int64_t* ptr, int32_t* col,
+    double* vals, int64_t capacity)
+{
+  using namespace fcg_amgs;
+  if (!h || level < 0 || which < 0 || which > 4) return -1;
+  const int nl = int(h->levels.size()) + 1;
+  if (level >= nl) return -1;
+  const Bsr& A = level == 0 ? h->A0 : h->levels[size_t(level - 1)].A;
+  const Bsr* M = nullptr;
+  const double* dv = nullptr;
+  int64_t count = 0;
+  if (which <= 2)
+  {
+    if (which != 0 && level + 1 >= nl) return -1;
+    M = which == 0 ? &A : which == 1 ? &h->steps[size_t(level)].P : &h->steps[size_t(level)].T;
+    dv = M->vals;
+    count = M->nnzb * M->br * M->bc;
+  }
+  else if (which == 3)
+  {
+    // the smoother's inverses: level 0 in the context's order smooths with the context's own
+    dv = level == 0 ? (h->new2old ? h->A0_dinv : h->ctx_dinv) : h->levels[size_t(level - 1)].dinv;
+    count = A.n * A.br * A.br;
+  }
+  else
+  {
+    const int64_t n = A.n * A.br;
+    if (level + 1 != nl || !h->cinv || h->cn != n) return -1;
+    dv = h->cinv;
+    count = n * n;
+  }
+  if (!ptr && !col && !vals) return count;
+  if (!vals || (M && (!ptr || !col)) || capacity < count || !h->ready || !h->local_ready) return -1;
+  if (!fcg_use_device(h->device)) return -1;
+  hipError_t he = hipDeviceSynchronize();
+  if (M)
+  {
+    if (he == hipSuccess) he = hipMemcpy(ptr, M->ptr, sizeof(int64_t) * size_t(M->n + 1), hipMemcpyDeviceToHost);
+    if (he == hipSuccess && M->nnzb) he = hipMemcpy(col, M->col, sizeof(int32_t) * size_t(M->nnzb), hipMemcpyDeviceToHost);
+  }
+  if (he == hipSuccess && count) he = hipMemcpy(vals, dv, sizeof(double) * size_t(count), hipMemcpyDeviceToHost);
+  if (he != hipSuccess)
+  {
+    (void)hipGetLastError();
+    return -1;
+  }
+  return count;
+}
+
+int fcg_amg_level_order(const fcg_amg* h, int32_t* new2old)
+{
+  if (!h || !new2old) return FCG_ERR_ARG;
+  if (!h->new2old)
+  {
+    for (int64_t p = 0; p < h->nb0; ++p) new2old[p] = int32_t(p);
+    return FCG_OK;
+  }
+  if (!fcg_use_device(h->device)) return fcg_device_error();
+  if (hipMemcpy(new2old, h->new2old, sizeof(int32_t) * size_t(h->nb0), hipMemcpyDeviceToHost) != hipSuccess)
+  {
+    (void)hipGetLastError();
+    return FCG_ERR_DEVICE;
+  }
+  return FCG_OK;
+}
 
 int fcg_amg_apply(fcg_amg* h, const double* d_K_vals, const double* d_r_row, double* d_z_row,
     void* stream)

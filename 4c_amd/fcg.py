@@ -161,6 +161,7 @@ EXPORTS = ["fcg_create", "fcg_destroy", "fcg_last_error", "fcg_evaluate", "fcg_e
            "fcg_bsr_to_dense", "fcg_amg_default_options", "fcg_amg_create", "fcg_amg_solve",
            "fcg_amg_levels", "fcg_amg_level_info", "fcg_amg_setup_ms", "fcg_amg_stats", "fcg_amg_last_error",
            "fcg_amg_destroy", "fcg_amg_setup", "fcg_amg_iterate", "fcg_amg_apply",
+           "fcg_amg_level_matrix", "fcg_amg_level_order",
            "fcg_amg_coupled_levels", "fcg_amg_coupled_stats", "fcg_comm_exchange_device",
            "fcg_transport_rccl", "fcg_dfcg_solve",
            "fcg_mass_assemble", "fcg_mass_nodal", "fcg_effective_tangent",
@@ -327,6 +328,9 @@ def lib():
     L.fcg_amg_last_error.restype = ctypes.c_char_p
     L.fcg_amg_destroy.argtypes = [vp]
     L.fcg_amg_apply.argtypes = [vp, vp, vp, vp, vp]
+    L.fcg_amg_level_matrix.argtypes = [vp, c_int, c_int, vp, vp, vp, i64]
+    L.fcg_amg_level_matrix.restype = i64
+    L.fcg_amg_level_order.argtypes = [vp, vp]
     L.fcg_amg_coupled_levels.argtypes = [vp]
     if hasattr(L, "fcg_amg_coupled_stats"):  # absent from older A/B builds (FCG_LIB)
         L.fcg_amg_coupled_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_int64), c_int]

@@ -575,6 +575,23 @@ double fcg_amg_setup_ms(const fcg_amg* amg);
  * pointer may be NULL.) */
 int fcg_amg_stats(const fcg_amg* amg, int* coarse_dense, int* graph_launches);
 const char* fcg_amg_last_error(const fcg_amg* amg);
+/* Host copies of what the last fcg_amg_setup left on the device (read-only: synchronises the
+ * device and copies; no kernel, nothing in the handle changes).  fcg_amg_level_matrix, `which`:
+ *   0  A_level in BSR (block row pointers, block columns, row-major blocks): level 0 in 3 x 3
+ *      blocks, the copy of K the hierarchy was built from, in level 0's order; 6 x 6 below
+ *   1  P_level and 2 T_level (the tentative prolongator), level < fcg_amg_levels() - 1: blocks of
+ *      3 x 6 on level 0, 6 x 6 below
+ *   3  the block inverses the level's smoother applies, [n][b][b] (ptr, col ignored)
+ *   4  the dense inverse of the coarsest level, n x n row-major (ptr, col ignored); only for the
+ *      last level and only when fcg_amg_stats reports coarse_dense
+ * Returns the number of doubles in vals (the blocks of ptr / col are that over the block's size);
+ * with ptr = col = vals = NULL only that count.  -1: no such level or matrix, capacity (doubles)
+ * below the count, no numeric setup of the handle's own hierarchy, or the copy failed.
+ * fcg_amg_level_order: new2old[p] = the context's node (block row) of level 0's node p, n0 / 3
+ * entries; the identity when level 0 keeps the context's order. */
+int64_t fcg_amg_level_matrix(const fcg_amg* amg, int level, int which, int64_t* ptr, int32_t* col,
+    double* vals, int64_t capacity);
+int fcg_amg_level_order(const fcg_amg* amg, int32_t* new2old);
 int fcg_amg_destroy(fcg_amg* amg);
 
 /* Neumann loads (host arrays; added into fext_row, owned rows only).  funct[d] > 0 selects a

@@ -1,0 +1,231 @@
+"""Host reference of the vector AMG's hierarchy and V-cycle (4c_amd/csrc/fcg_amg_solver.hip), the
+block counterpart of samg_ref.py: BSR level matrices as dense arrays in float64 or longdouble, the
+float64 replay of the per-block Gauss-Jordan of bsr_block_inverse_kernel, the Morton order and the
+near-null space of fcg_amg_create, and the V-cycle rebuilt from the level matrices A_l, the
+prolongators P_l, block inverses, lambda_max estimates and options the library reports --
+samg_ref.cheb's recurrence with block Jacobi in place of the diagonal, the residual restricted by
+P^T, a dense inverse on the coarsest level.  TEST INFRASTRUCTURE."""
+
+import importlib
+
+import numpy as np
+import scipy.sparse as sp
+
+import samg_ref
+from samg_ref import LD
+
+amg = importlib.import_module("4c_amd.amg")
+U = 2.0 ** -53
+
+
+def bsr_dense(ptr, col, vals, n_bcols, dtype=np.float64):
+    """Dense copy of a BSR matrix, vals [blocks][br][bc]."""
+    ptr = np.asarray(ptr, dtype=np.int64)
+    vals = np.asarray(vals)
+    n, (br, bc) = len(ptr) - 1, vals.shape[1:]
+    D = np.zeros((n, br, int(n_bcols), bc), dtype=dtype)
+    D[np.repeat(np.arange(n), np.diff(ptr)), :, np.asarray(col), :] = vals.astype(dtype)
+    return D.reshape(n * br, int(n_bcols) * bc)
+
+
+def bsr_pattern(ptr, col, n_bcols):
+    """Boolean [n][n_bcols] block pattern."""
+    ptr = np.asarray(ptr, dtype=np.int64)
+    n = len(ptr) - 1
+    S = np.zeros((n, int(n_bcols)), dtype=bool)
+    S[np.repeat(np.arange(n), np.diff(ptr)), np.asarray(col)] = True
+    return S
+
+
+def diag_blocks(ptr, col, vals):
+    """[n][b][b] diagonal blocks of a square BSR matrix."""
+    ptr = np.asarray(ptr, dtype=np.int64)
+    rows = np.repeat(np.arange(len(ptr) - 1), np.diff(ptr))
+    hit = np.nonzero(np.asarray(col) == rows)[0]
+    assert np.array_equal(rows[hit], np.arange(len(ptr) - 1))
+    return np.asarray(vals)[hit]
+
+
+def block_diag_dense(blocks, dtype=np.float64):
+    n, b, _ = blocks.shape
+    D = np.zeros((n, b, n, b), dtype=dtype)
+    D[np.arange(n), :, np.arange(n), :] = blocks.astype(dtype)
+    return D.reshape(n * b, n * b)
+
+
+def gauss_jordan_f64(D):
+    """float64 replay of bsr_block_inverse_kernel on the blocks D [n][b][b]: Gauss-Jordan in the
+    kernel's pivot order (0 .. b - 1, no pivoting), the pivot row scaled by 1 / pivot, every
+    product and difference rounded once (no fused multiply-add)."""
+    a = np.array(D, dtype=np.float64)
+    n, b, _ = a.shape
+    v = np.broadcast_to(np.eye(b), a.shape).copy()
+    for p in range(b):
+        ip = 1.0 / a[:, p, p]
+        a[:, p, :] *= ip[:, None]
+        v[:, p, :] *= ip[:, None]
+        for r in range(b):
+            if r == p:
+                continue
+            f = a[:, r, p].copy()
+            a[:, r, :] -= f[:, None] * a[:, p, :]
+            v[:, r, :] -= f[:, None] * v[:, p, :]
+    return v
+
+
+def block_inverse_ld(D):
+    """(inverses longdouble [n][b][b], kappa_inf float64 [n]) of the blocks D: numpy's float64
+    inverses refined by two Newton steps in longdouble, as samg_ref.inverse."""
+    D = np.asarray(D, dtype=np.float64)
+    X = np.linalg.inv(D).astype(LD)
+    Dl, I = D.astype(LD), np.eye(D.shape[1], dtype=LD)
+    for _ in range(2):
+        X = X + np.matmul(X, I - np.matmul(Dl, X))
+    ninf = lambda M: np.abs(M).sum(axis=2).max(axis=1)
+    return X, (ninf(Dl) * ninf(X)).astype(np.float64)
+
+
+def morton_order(x):
+    """new2old of fcg_amg_create: the nodes x [n][3] sorted (stably) by their Morton key -- 21 bits
+    per axis, floor(f 2097151) of the coordinate's fraction f of the bounding box, x the most
+    significant bit of each triple."""
+    x = np.asarray(x, dtype=np.float64)
+    lo, hi = x.min(axis=0), x.max(axis=0)
+    ext = hi - lo
+    f = np.where(ext > 0, (x - lo) / np.where(ext > 0, ext, 1.0), 0.0)
+    q = np.minimum(2097151.0, np.maximum(0.0, f * 2097151.0)).astype(np.uint64)
+    key = np.zeros(len(x), dtype=np.uint64)
+    for bit in range(20, -1, -1):
+        for d in range(3):
+            key = (key << np.uint64(1)) | ((q[:, d] >> np.uint64(bit)) & np.uint64(1))
+    return np.argsort(key, kind="stable").astype(np.int32)
+
+
+def near_null_space(x, dbc):
+    """fcg_amg_create's level-0 near-null space [n][3][6] at the nodes x [n][3] (level 0's order):
+    the rigid-body modes about the centroid -- summed node by node as the library does, which a
+    pairwise mean would not reproduce bitwise -- with the rows of the Dirichlet DOFs dbc [n][3]
+    zeroed; and the nodes it leaves out of the aggregation (all three DOFs fixed)."""
+    x = np.asarray(x, dtype=np.float64)
+    n = len(x)
+    cen = np.cumsum(x / float(n), axis=0)[-1]
+    c = x - cen
+    B = np.zeros((n, 3, 6))
+    B[:, 0, 0] = B[:, 1, 1] = B[:, 2, 2] = 1.0
+    B[:, 0, 3], B[:, 1, 3] = -c[:, 1], c[:, 0]
+    B[:, 1, 4], B[:, 2, 4] = -c[:, 2], c[:, 1]
+    B[:, 0, 5], B[:, 2, 5] = c[:, 2], -c[:, 0]
+    dbc = np.asarray(dbc, dtype=bool).reshape(n, 3)
+    B[dbc] = 0.0
+    return B, dbc.all(axis=1)
+
+
+def node_blocks(rowptr, col_lid, vals, n_rows):
+    """The owned block of a context's node-triple CSR matrix (rows 3b .. 3b + 2 share one pattern of
+    column triples; columns >= n_rows are ghosts and dropped) as BSR: (ptr, col, vals [blocks][3][3])
+    in the context's order."""
+    rp = np.asarray(rowptr, dtype=np.int64)
+    cl = np.asarray(col_lid, dtype=np.int64)
+    nn = int(n_rows) // 3
+    cnt = (rp[1:3 * nn:3] - rp[0:3 * nn:3]) // 3
+    owner = np.repeat(np.arange(nn), cnt)
+    k = np.arange(int(cnt.sum())) - np.repeat(np.cumsum(cnt) - cnt, cnt)
+    c0 = cl[rp[3 * owner] + 3 * k]
+    pos = rp[3 * owner[:, None] + np.arange(3)][:, :, None] + 3 * k[:, None, None] + np.arange(3)
+    keep = c0 < n_rows
+    ptr = np.concatenate([[0], np.cumsum(np.bincount(owner[keep], minlength=nn))]).astype(np.int64)
+    return ptr, (c0[keep] // 3).astype(np.int32), np.asarray(vals)[pos[keep]]
+
+
+def permute_bsr(ptr, col, vals, new2old):
+    """P A P^T of a square BSR matrix: block (p, q) = block (new2old[p], new2old[q]), columns
+    ascending in every row."""
+    n = len(ptr) - 1
+    old2new = np.empty(n, dtype=np.int64)
+    old2new[np.asarray(new2old)] = np.arange(n)
+    r = old2new[np.repeat(np.arange(n), np.diff(ptr))]
+    c = old2new[np.asarray(col)]
+    o = np.lexsort((c, r))
+    nptr = np.concatenate([[0], np.cumsum(np.bincount(r, minlength=n))]).astype(np.int64)
+    return nptr, c[o].astype(np.int32), np.asarray(vals)[o]
+
+
+def bsr_sparse(ptr, col, vals, n_bcols, dtype=np.float64):
+    """scipy CSR copy of a BSR matrix in `dtype` (stored zeros kept)."""
+    vals = np.asarray(vals)
+    n, (br, bc) = len(ptr) - 1, vals.shape[1:]
+    return sp.bsr_matrix((vals.astype(dtype), np.asarray(col), np.asarray(ptr)),
+                         shape=(n * br, int(n_bcols) * bc)).tocsr()
+
+
+def block_diag_sparse(blocks, dtype=np.float64):
+    n = len(blocks)
+    return bsr_sparse(np.arange(n + 1), np.arange(n), blocks, n, dtype)
+
+
+def coarsen_step(ptr, col, ns, skip=None):
+    """One step of the library's coarsen() on the block graph (ptr, col) with the near-null space
+    ns [n][bs][6], by the library's own host routines: the aggregates, the tentative prolongator
+    T in BSR, the coarse near-null space, the count of vanished columns, and the patterns of
+    P (= A T) and of A_c = P^T (A P)."""
+    n = len(ptr) - 1
+    agg, n_agg = amg.aggregate(ptr, col, skip)
+    tent, nsc, nd = amg.tentative(ns, agg, n_agg)
+    has = agg >= 0
+    tptr = np.concatenate([[0], np.cumsum(has)]).astype(np.int64)
+    tcol = agg[has].astype(np.int32)
+    pp, pc = amg.symbolic(ptr, col, tptr, tcol, n_agg)
+    app, apc = amg.symbolic(ptr, col, pp, pc, n_agg)
+    tp, tc, _ = amg.transpose_pattern(pp, pc, n_agg)
+    cp, cc = amg.symbolic(tp, tc, app, apc, n_agg)
+    assert len(tp) == n_agg + 1 and len(pp) == n + 1
+    return {"agg": agg, "n_agg": n_agg, "T": (tptr, tcol, tent[has]), "ns": nsc, "deficient": nd,
+            "P": (pp, pc), "Ac": (cp, cc)}
+
+
+class BlockJacobi:
+    """The `dinv` of samg_ref.cheb for block Jacobi: r * dinv applies the blocks [n][b][b] to the
+    vector r (or to every column of a matrix)."""
+
+    __array_ufunc__ = None  # numpy defers r * self to __rmul__
+
+    def __init__(self, blocks, dtype):
+        self.d = np.asarray(blocks).astype(dtype)
+
+    def __rmul__(self, r):
+        n, b, _ = self.d.shape
+        return np.matmul(self.d, r.reshape(n, b, -1)).reshape(r.shape)
+
+
+class Cycle:
+    """A[l] dense level matrices, P[l] dense prolongators (len(A) - 1 of them), dinv[l] the block
+    inverses [n_l][b][b] of the smoothed levels, lmax[l] the library's estimates, nu / ratio /
+    boost its options.  The matrices may be scipy sparse.  The coarsest level is applied through
+    samg_ref.inverse of A[-1] (cinv: that inverse, when the caller already has it)."""
+
+    def __init__(self, A, P, dinv, lmax, nu, ratio, boost, dtype, cinv=None):
+        assert len(A) >= 2 and len(P) == len(A) - 1 and len(dinv) >= len(P)
+        cast = lambda m: m.astype(dtype) if sp.issparse(m) else np.asarray(m).astype(dtype)
+        self.dtype = dtype
+        self.A = [cast(a) for a in A]
+        self.P = [cast(p) for p in P]
+        self.dinv = [BlockJacobi(d, dtype) for d in dinv[:len(P)]]
+        self.lmax, self.nu, self.ratio, self.boost = lmax, nu, ratio, boost
+        last = self.A[-1].toarray() if sp.issparse(self.A[-1]) else self.A[-1]
+        self.cinv = samg_ref.inverse(last, dtype) if cinv is None else np.asarray(cinv).astype(dtype)
+
+    def _cheb(self, l, b, x):
+        return samg_ref.cheb(self.A[l], self.dinv[l], b, x, self.lmax[l], self.nu, self.ratio, self.boost,
+                             self.dtype)
+
+    def apply(self, b, l=0):
+        """One V-cycle of b: a vector, or a matrix of right-hand sides as columns."""
+        b = np.asarray(b).astype(self.dtype)
+        if l == len(self.A) - 1:
+            return self.cinv @ b
+        x = self._cheb(l, b, None)
+        xc = self.apply(self.P[l].T @ (b - self.A[l] @ x), l + 1)
+        return self._cheb(l, b, x + self.P[l] @ xc)
+
+    def matrix(self):
+        return self.apply(np.eye(self.A[0].shape[0], dtype=self.dtype))

@@ -149,9 +149,7 @@ if a.amg_s:
     amg_s = amg_mod.NativeAMG(m, ev, rows_s)
     amg_out["amg_s"] = {"create_s": time.perf_counter() - t, "setup_ms": setup_ms(amg_s, K["Kss"]),
                         "levels": [l["dofs"] for l in amg_s.describe()]}
-    apply_s = lambda K_, r, z: fcg.lib().fcg_amg_apply(amg_s._h, K_.data_ptr(), r.data_ptr(), z.data_ptr(),
-                                                       torch.cuda.current_stream(dev).cuda_stream)
-    amg_out["amg_s"]["vcycle_ms"] = cycle_ms(apply_s, K["Kss"], fs, torch.zeros_like(fs))
+    amg_out["amg_s"]["vcycle_ms"] = cycle_ms(amg_s.apply, K["Kss"], fs, torch.zeros_like(fs))
 if a.amg_t:
     t = time.perf_counter()
     amg_t = amg_mod.ScalarAMG(tev, rows_t)
