@@ -403,7 +403,7 @@ class AMG(CycleFCG):
 
 class NativeAMG:
     """The same smoothed-aggregation AMG solve as one native object behind the C ABI
-    (fcg_amg_create / fcg_amg_solve, fcg_amg_solver.hip) -- what a C++ host calls; the coarsest
+    (fcg_amg_create / fcg_amg_solve, fcg_amg_api.hip) -- what a C++ host calls; the coarsest
     level is solved by block-Jacobi CG to coarse_rtol instead of a dense factor.  Same interface
     as AMG: solve(K, b, x, rtol, max_iter) -> (iterations, relative residual)."""
 

@@ -7,7 +7,7 @@
 //   * the preconditioner: the rank's fcg_amg -- aggregation and level-0 smoothing on the owned
 //     block (MueLu's uncoupled aggregation also aggregates within a rank), the coarse levels
 //     coupled across the ranks (A_1 = P_0^T A P_0 of the global operator, gathered and solved
-//     redundantly; fcg_amgs::Coupled in fcg_amg_solver.hip) when the transport names its rank and
+//     redundantly; fcg_amgs::Coupled in fcg_amg_coupled.hip) when the transport names its rank and
 //     rank count -- or the nodal block Jacobi;
 //   * the inner products are fixed-order partial sums on each rank plus one all-reduce of a small
 //     device buffer (two per iteration), so the iterates are independent of the launch geometry.

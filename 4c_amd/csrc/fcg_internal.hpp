@@ -298,7 +298,7 @@ struct fcg_ctx {
   double create_phase_s[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // fcg_get_create_phases
 };
 
-// fcg_dfcg_solve's AMG preconditioner (fcg_amg_solver.hip; not part of the C ABI): numeric setup
+// fcg_dfcg_solve's AMG preconditioner (fcg_amg_api.hip; not part of the C ABI): numeric setup
 // and one application, with the coarse levels coupled across the ranks of the transport when the
 // handle is rank-local (fcg_amgs::Coupled), else the handle's own V-cycle
 extern "C" {

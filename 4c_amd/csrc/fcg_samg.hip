@@ -16,8 +16,10 @@
 //   scsr_cheb_kernel   one Chebyshev degree fused: r_i = b_i - (A x)_i, d_i = c_d d_i + c_r r_i /
 //                      a_ii, x'_i = x_i + d_i, x' a second buffer (the two ping-pong, so the kernel
 //                      never reads an x it has written).  One pass over A's row per degree against
-//                      the five launches and vector passes of cheb() in fcg_amg_solver.hip, whose
-//                      recurrence (theta, delta, sigma, rho) this one follows exactly.
+//                      the five launches and vector passes of cheb() in fcg_amg_solver.hip; both
+//                      take their coefficients from fcg_amgs::ChebCoef.
+// The dot product, the vector update, the flexible-CG steps, the Lanczos recurrence and the dense
+// coarsest level are the structural AMG's, through fcg_amg_shared.hpp (fcg_amg_vec.hip).
 // Byte model of a level-0 smoother degree: 12 bytes per non-zero (value + column) plus about 40
 // bytes per row (b, x, d read, d, x' written; the row pointer and 1 / a_ii on top), the gathered
 // x mostly from L2.
@@ -38,11 +40,9 @@
 
 namespace fcg_samgs {
 
-constexpr int kBlock = 256;
-constexpr int kMaxPartials = 1024;
+using fcg_amgs::kBlock;
 
 inline unsigned blocks_for(int64_t n) { return unsigned(std::max<int64_t>(1, (n + kBlock - 1) / kBlock)); }
-inline unsigned capped(int64_t n) { return unsigned(std::max<int64_t>(1, std::min<int64_t>(kMaxPartials, (n + kBlock - 1) / kBlock))); }
 // lanes per row for a matrix whose longest row has w entries
 inline int lanes_for(int w) { return w <= 8 ? 4 : w <= 48 ? 16 : 64; }
 
@@ -176,49 +176,6 @@ __global__ __launch_bounds__(kBlock) void to_dense_kernel(int64_t n, const int64
   for (int64_t k = ptr[i]; k < ptr[i + 1]; ++k) D[i * n + col[k]] = vals[k];
 }
 
-__device__ inline double block_sum(double v, double* sbuf)
-{
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) sbuf[w] = v;
-  __syncthreads();
-  double t = 0.0;
-  if (threadIdx.x == 0)
-    for (int i = 0; i < kBlock / 64; ++i) t += sbuf[i];
-  __syncthreads();
-  return t;
-}
-
-// partial[block] = the block's grid-stride share of a . b (fixed assignment), then one block sums
-__global__ __launch_bounds__(kBlock) void dot_kernel(const double* __restrict__ a, const double* __restrict__ b,
-    int64_t n, double* partial)
-{
-  __shared__ double sbuf[kBlock / 64];
-  double t = 0.0;
-  for (int64_t i = int64_t(blockIdx.x) * kBlock + threadIdx.x; i < n; i += int64_t(gridDim.x) * kBlock)
-    t += a[i] * b[i];
-  const double s = block_sum(t, sbuf);
-  if (threadIdx.x == 0) partial[blockIdx.x] = s;
-}
-
-__global__ __launch_bounds__(kBlock) void reduce_kernel(const double* __restrict__ partial, int n, double* out)
-{
-  __shared__ double sbuf[kBlock / 64];
-  double t = 0.0;
-  for (int i = threadIdx.x; i < n; i += kBlock) t += partial[i];
-  const double s = block_sum(t, sbuf);
-  if (threadIdx.x == 0) *out = s;
-}
-
-// y = a x + b y
-__global__ __launch_bounds__(kBlock) void axpby_kernel(double a, const double* __restrict__ x, double b,
-    double* y, int64_t n)
-{
-  const int64_t i = int64_t(blockIdx.x) * kBlock + threadIdx.x;
-  if (i < n) y[i] = a * x[i] + b * y[i];
-}
-
 // z = dinv .* r
 __global__ __launch_bounds__(kBlock) void scale_kernel(const double* __restrict__ dinv,
     const double* __restrict__ r, double* __restrict__ z, int64_t n)
@@ -239,27 +196,6 @@ __global__ __launch_bounds__(kBlock) void random_kernel(double* v, const uint8_t
   const double u = double(h >> 11) * (1.0 / 9007199254740992.0) - 0.5;
   v[i] = skip && skip[i] ? 0.0 : u;
 }
-
-// flexible CG, scalars on the device: sc[0] r.z, sc[1] p.q, sc[2] r.z new, sc[3] r.r, sc[5] z.r_old
-__global__ __launch_bounds__(kBlock) void fcg_step_kernel(const double* __restrict__ sc,
-    const double* __restrict__ p, const double* __restrict__ q, double* x, double* r, double* r_old, int64_t n)
-{
-  const int64_t i = int64_t(blockIdx.x) * kBlock + threadIdx.x;
-  if (i >= n) return;
-  const double alpha = sc[0] / sc[1];
-  x[i] += alpha * p[i];
-  r_old[i] = r[i];
-  r[i] -= alpha * q[i];
-}
-__global__ __launch_bounds__(kBlock) void fcg_dir_kernel(const double* __restrict__ sc,
-    const double* __restrict__ z, double* p, int64_t n)
-{
-  const int64_t i = int64_t(blockIdx.x) * kBlock + threadIdx.x;
-  if (i >= n) return;
-  const double beta = (sc[2] - sc[5]) / sc[0];
-  p[i] = z[i] + beta * p[i];
-}
-__global__ void shift_kernel(double* sc) { sc[0] = sc[2]; }
 
 struct Fail {
   int code;
@@ -394,25 +330,17 @@ void upload_pattern(fcg_samg* h, const Pattern& P, DCsr& D, bool with_vals)
 
 double dot_host(fcg_samg* h, const double* a, const double* b, int64_t n, hipStream_t s)
 {
-  const unsigned g = capped(n);
-  hipLaunchKernelGGL(dot_kernel, dim3(g), dim3(kBlock), 0, s, a, b, n, h->partial);
-  hipLaunchKernelGGL(reduce_kernel, dim3(1), dim3(kBlock), 0, s, h->partial, int(g), h->sc + 6);
-  double v = 0.0;
-  ck(hipMemcpyAsync(&v, h->sc + 6, sizeof(double), hipMemcpyDeviceToHost, s), "hipMemcpyAsync");
-  ck(hipStreamSynchronize(s), "hipStreamSynchronize");
-  return v;
+  return fcg_amgs::dot_host(a, b, n, h->partial, h->sc + 6, s, ck);
 }
 void dot_dev(fcg_samg* h, const double* a, const double* b, int64_t n, double* out, hipStream_t s)
 {
-  const unsigned g = capped(n);
-  hipLaunchKernelGGL(dot_kernel, dim3(g), dim3(kBlock), 0, s, a, b, n, h->partial);
-  hipLaunchKernelGGL(reduce_kernel, dim3(1), dim3(kBlock), 0, s, h->partial, int(g), out);
+  fcg_amgs::dot(a, b, n, h->partial, out, s);
 }
 
 inline const double* vals_of(const fcg_samg* h, int l, const double* K) { return l == 0 ? K : h->levels[size_t(l)].A.vals; }
 
-// lambda_max(D^-1 A) of level l by the 10-step Lanczos of the structural AMG's estimate_lmax
-// (Jacobi-preconditioned CG on a fixed random vector, zero on level 0's Dirichlet rows); the
+// lambda_max(D^-1 A) of level l by the 10-step Lanczos both AMGs run (fcg_amgs::lanczos_steps:
+// Jacobi-preconditioned CG, here on a fixed random vector, zero on level 0's Dirichlet rows); the
 // tridiagonal's largest eigenvalue by the shared Sturm bisection
 void estimate_lmax(fcg_samg* h, int l, const double* K, hipStream_t s)
 {
@@ -425,28 +353,12 @@ void estimate_lmax(fcg_samg* h, int l, const double* K, hipStream_t s)
   hipLaunchKernelGGL(random_kernel, g, bl, 0, s, r, l == 0 ? h->skip : nullptr, n);
   hipLaunchKernelGGL(scale_kernel, g, bl, 0, s, L.dinv, r, z, n);
   ck(hipMemcpyAsync(p, z, sizeof(double) * size_t(n), hipMemcpyDeviceToDevice, s), "copy");
-  double rz = dot_host(h, r, z, n, s);
-  std::vector<double> al, be;
-  for (int it = 0; it < 10; ++it)
-  {
-    launch_spmv(L.A, vals, p, nullptr, q, 1.0, 0, s);
-    const double pq = dot_host(h, p, q, n, s);
-    if (!(pq > 0.0))
-    {
-      if (al.empty()) throw Fail{FCG_ERR_SINGULAR, "scalar AMG Lanczos estimate on level " + std::to_string(l) + ": p.Ap <= 0"};
-      break;
-    }
-    const double alpha = rz / pq;
-    hipLaunchKernelGGL(axpby_kernel, g, bl, 0, s, -alpha, q, 1.0, r, n);
-    hipLaunchKernelGGL(scale_kernel, g, bl, 0, s, L.dinv, r, z, n);
-    const double rzn = dot_host(h, r, z, n, s);
-    al.push_back(alpha);
-    if (!(rzn > 0.0)) break;
-    be.push_back(rzn / rz);
-    hipLaunchKernelGGL(axpby_kernel, g, bl, 0, s, 1.0, z, rzn / rz, p, n);
-    rz = rzn;
-  }
-  L.lmax = fcg_amgs::lanczos_lmax(al, be);
+  const fcg_amgs::LanczosSteps t = fcg_amgs::lanczos_steps(
+      [&](const double* x, double* y) { launch_spmv(L.A, vals, x, nullptr, y, 1.0, 0, s); },
+      [&](const double* x, double* y) { hipLaunchKernelGGL(scale_kernel, g, bl, 0, s, L.dinv, x, y, n); },
+      [&](const double* x, const double* y) { return dot_host(h, x, y, n, s); }, r, z, p, q, n, s);
+  if (t.al.empty()) throw Fail{FCG_ERR_SINGULAR, "scalar AMG Lanczos estimate on level " + std::to_string(l) + ": p.Ap <= 0"};
+  L.lmax = fcg_amgs::lanczos_lmax(t.al, t.be);
   if (!(L.lmax > 0.0) || !std::isfinite(L.lmax))
     throw Fail{FCG_ERR_SINGULAR, "scalar AMG: lambda_max estimate of level " + std::to_string(l) + " is not positive"};
 }
@@ -529,20 +441,15 @@ double* cheb(fcg_samg* h, int l, const double* K, const double* b, const double*
   const fcg_amg_options& op = h->opt;
   const DLevel& L = h->levels[size_t(l)];
   const double* vals = vals_of(h, l, K);
-  const double lmax = op.boost * L.lmax;
-  const double lmin = lmax / op.ratio;
-  const double theta = 0.5 * (lmax + lmin), delta = 0.5 * (lmax - lmin);
-  const double sigma = theta / delta;
-  double rho = 1.0 / sigma;
+  fcg_amgs::ChebCoef c(L.lmax, op.boost, op.ratio);
   double* out = buf0;
-  launch_cheb(L.A, vals, L.dinv, b, from, d, out, 0.0, 1.0 / theta, from ? 0 : 2, s);
+  launch_cheb(L.A, vals, L.dinv, b, from, d, out, 0.0, c.first(), from ? 0 : 2, s);
   for (int k = 1; k < op.nu; ++k)
   {
-    const double rho_n = 1.0 / (2.0 * sigma - rho);
+    const fcg_amgs::ChebCoef::Degree g = c.next();
     double* nxt = out == buf0 ? buf1 : buf0;
-    launch_cheb(L.A, vals, L.dinv, b, out, d, nxt, rho_n * rho, 2.0 * rho_n / delta, 1, s);
+    launch_cheb(L.A, vals, L.dinv, b, out, d, nxt, g.c_d, g.c_r, 1, s);
     out = nxt;
-    rho = rho_n;
   }
   return out;
 }
@@ -585,7 +492,6 @@ void run_fcg(fcg_samg* h, const double* K, const double* b, double* x, double rt
 {
   DLevel& L = h->levels[0];
   const int64_t n = L.A.n;
-  const dim3 g(blocks_for(n)), bl(kBlock);
   double *r = L.v[3], *z = L.v[4], *p = L.v[5], *q = L.v[6], *ro = L.v[7];
   double* sc = h->sc;
   *iterations = 0;
@@ -608,7 +514,7 @@ void run_fcg(fcg_samg* h, const double* K, const double* b, double* x, double rt
     ++it;
     launch_spmv(L.A, K, p, nullptr, q, 1.0, 0, s);
     dot_dev(h, p, q, n, sc + 1, s);
-    hipLaunchKernelGGL(fcg_step_kernel, g, bl, 0, s, sc, p, q, x, r, ro, n);
+    fcg_amgs::fcg_step(sc, p, q, x, r, ro, n, s);
     dot_dev(h, r, r, n, sc + 3, s);
     vcycle(h, 0, K, r, z, L.v[0], s);
     dot_dev(h, r, z, n, sc + 2, s);
@@ -620,8 +526,8 @@ void run_fcg(fcg_samg* h, const double* K, const double* b, double* x, double rt
     if (!std::isfinite(rn)) throw Fail{FCG_ERR_SINGULAR, "fcg_samg_solve: non-finite residual"};
     if (rn <= rtol * bn) break;
     if (!(hs[2] > 0.0)) throw Fail{FCG_ERR_SINGULAR, "fcg_samg_solve: indefinite V-cycle (r.z <= 0)"};
-    hipLaunchKernelGGL(fcg_dir_kernel, g, bl, 0, s, sc, z, p, n);
-    hipLaunchKernelGGL(shift_kernel, dim3(1), dim3(1), 0, s, sc);
+    fcg_amgs::fcg_dir(sc, z, p, n, s);
+    fcg_amgs::fcg_shift(sc, s);
   }
   // the true residual at return
   launch_spmv(L.A, K, x, b, r, 1.0, 2, s);
@@ -760,7 +666,7 @@ int fcg_samg_create(fcg_tsi_ctx* tctx, const int64_t* rowptr_tt, const int32_t* 
       st.pAc.b = upload(h, ps.pAc.b);
     }
     h->skip = upload(h, skip);
-    h->partial = dalloc<double>(h, kMaxPartials);
+    h->partial = dalloc<double>(h, fcg_amgs::kMaxPartials);
     h->sc = dalloc<double>(h, 8);
     h->flag = dalloc<int32_t>(h, 1);
     if (ns)

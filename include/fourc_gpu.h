@@ -532,8 +532,9 @@ int fcg_amg_smooth_prolongator(int device, int br, int64_t n_brows, const int64_
 int fcg_bsr_to_dense(int device, int b, int64_t n_brows, const int64_t* d_ptr, const int32_t* d_col,
     const double* d_vals, double* d_dense, void* stream);
 
-/* The smoothed-aggregation AMG solve as one native object (fcg_amg_solver.hip): what a C++ host
- * calls instead of its Belos CG + MueLu preconditioner on a tangent the context assembled.
+/* The smoothed-aggregation AMG solve as one native object (fcg_amg_api.hip, over fcg_amg_solver.hip
+ * and fcg_amg_coupled.hip): what a C++ host calls instead of its Belos CG + MueLu preconditioner on
+ * a tangent the context assembled.
  * fcg_amg_create: the context's own CSR graph (host rowptr / col_lid as in fcg_desc; rows 3b..3b+2
  * = the DOFs of block row b, single rank), node_x[b][3] the reference coordinates of block row b's
  * node, the Dirichlet rows (unit rows of K); builds the hierarchy's patterns on the host.  A

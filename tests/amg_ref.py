@@ -1,7 +1,7 @@
 """Host reference of the vector AMG's hierarchy and V-cycle (4c_amd/csrc/fcg_amg_solver.hip), the
 block counterpart of samg_ref.py: BSR level matrices as dense arrays in float64 or longdouble, the
 float64 replay of the per-block Gauss-Jordan of bsr_block_inverse_kernel, the Morton order and the
-near-null space of fcg_amg_create, and the V-cycle rebuilt from the level matrices A_l, the
+near-null space of fcg_amg_create (fcg_amg_api.hip), and the V-cycle rebuilt from the level matrices A_l, the
 prolongators P_l, block inverses, lambda_max estimates and options the library reports --
 samg_ref.cheb's recurrence with block Jacobi in place of the diagonal, the residual restricted by
 P^T, a dense inverse on the coarsest level.  TEST INFRASTRUCTURE."""

@@ -1,6 +1,6 @@
 """Host reference of the scalar AMG's V-cycle (4c_amd/csrc/fcg_samg.hip): the cycle rebuilt in numpy
 from the level matrices A_l and prolongators P_l the library reports (dense here), its lambda_max
-estimates and its options -- the Chebyshev recurrence of cheb() in fcg_amg_solver.hip (theta,
+estimates and its options -- the Chebyshev recurrence of ChebCoef in fcg_amg_shared.hpp (theta,
 delta, sigma, rho), Jacobi scaling, the residual restricted by P^T, a dense inverse on the coarsest
 level -- in float64 or in longdouble.  TEST INFRASTRUCTURE."""
 
