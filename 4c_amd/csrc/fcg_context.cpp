@@ -264,7 +264,7 @@ void upload_common(Uploader& U, const fcg_desc* d, const plan::NodeRows& N, int6
       hipHostMallocDefault);
 }
 
-void upload_structured(Uploader& U, const fcg_desc* d, const plan::NodeRows& N, const plan::StructHost& sp)
+void upload_structured(Uploader& U, const fcg_desc* d, const plan::StructHost& sp)
 {
   fcg::DeviceMesh& m = U.ctx->mesh;
   m.path = FCG_PATH_STRUCTURED;
@@ -276,23 +276,28 @@ void upload_structured(Uploader& U, const fcg_desc* d, const plan::NodeRows& N, 
   m.NI = sp.n[0]; m.NJ = sp.n[1]; m.NK = sp.n[2];
   m.EX0 = sp.elo[0]; m.EY0 = sp.elo[1]; m.EZ0 = sp.elo[2];
   m.EX = sp.en[0]; m.EY = sp.en[1]; m.EZ = sp.en[2];
-  // rows not in lattice order (input-file numbering): the linear sweep defers each row's
-  // lower-plane blocks by one layer (MODE 3; renumbered 1M box: 3.41 -> 2.23 GB written,
-  // 1.45 -> 1.30-1.35 ms, profiles/r03/defer/).  TotLag keeps MODE 0: its sweep is bound by the
-  // arithmetic at one workgroup per CU, and the extra LDS round trip cost 4-6 % there.
-  // FCG_SWEEP_DEFER=0/1 forces the choice (A/B runs, tests)
+  // The linear sweep defers each row's lower-plane blocks by one layer (MODE 3), so that a row's
+  // cache lines are filled within one layer: rows not in lattice order (input-file numbering,
+  // renumbered 1M box: 3.41 -> 2.23 GB written, 1.45 -> 1.30-1.35 ms, profiles/r03/defer/) and,
+  // since the deferred kernel has the regular-layer emit and the branch-free hold, lattice-ordered
+  // rows too (1M box: 2.34 -> 2.04 GB written, profiles/sweep_rows/).  TotLag keeps MODE 0: its
+  // sweep is bound by the arithmetic at one workgroup per CU, and the extra LDS round trip cost
+  // 4-6 % there.  FCG_SWEEP_DEFER=0/1 forces the choice (A/B runs, tests)
   const char* de = std::getenv("FCG_SWEEP_DEFER");
-  m.sweep_defer = de && de[0] ? de[0] == '1'
-                              : d->kinematics == FCG_LINEAR && 8 * sp.rows_unordered > N.nrn();
+  m.sweep_defer = de && de[0] ? de[0] == '1' : d->kinematics == FCG_LINEAR;
+  // FCG_SWEEP_SKIP_EMPTY=0: the element-free layers run as every other layer (A/B runs, tests)
+  const char* se = std::getenv("FCG_SWEEP_SKIP_EMPTY");
+  m.sweep_skip_empty = !(se && se[0] == '0');
   U.up(&m.elem_at, sp.elem_at);
   U.up(&m.lat_x, sp.lat_x);
   U.up(&m.lat_dof, sp.lat_dof);
   U.up(&m.plane_rec, sp.plane_rec);
-  // regular lattice tiles (classify_regular_tiles): the unchecked linear MODE-0 kernels take their
-  // closed-form row bookkeeping for the layers inside a tile's run.  A context that launches other
-  // kernels, or FCG_SWEEP_REGULAR=0 at fcg_create (A/B runs, tests), gets empty runs: today's path
+  // regular lattice tiles (classify_regular_tiles): the unchecked linear kernels (MODE 0 and the
+  // deferred MODE 3) take their closed-form row bookkeeping for the layers inside a tile's run.  A
+  // context that launches other kernels, or FCG_SWEEP_REGULAR=0 at fcg_create (A/B runs, tests),
+  // gets empty runs: the records' path
   const char* rg = std::getenv("FCG_SWEEP_REGULAR");
-  const bool regular = !(rg && rg[0] == '0') && d->kinematics == FCG_LINEAR && !m.sweep_defer;
+  const bool regular = !(rg && rg[0] == '0') && d->kinematics == FCG_LINEAR;
   m.layers_total = sp.layers_total;
   m.reg_layers = regular ? sp.reg_layers : 0;
   if (m.reg_layers > 0)
@@ -507,7 +512,7 @@ int fcg_create(const fcg_desc* d, fcg_ctx** out)
   upload_common(U, d, rows, inc.n_inc);
   switch (choice.path())
   {
-    case FCG_PATH_STRUCTURED: upload_structured(U, d, rows, choice.sp); break;
+    case FCG_PATH_STRUCTURED: upload_structured(U, d, choice.sp); break;
     case FCG_PATH_COLORED: upload_colored(U, d, inc, choice.cp); break;
     case FCG_PATH_GATHER: upload_gather(U, d, gather); break;
     default: upload_general(U, d, inc, h27_order, dev);
@@ -895,6 +900,9 @@ int fcg_get_diagnostics(const fcg_ctx* ctx, uint64_t* out, int n)
   // that take the regular-tile path (none in a context that keeps the checked kernels), and all
   v[13] = m.path == FCG_PATH_STRUCTURED && !m.sweep_checked ? uint64_t(m.reg_layers) : 0;
   v[14] = m.path == FCG_PATH_STRUCTURED ? uint64_t(m.layers_total) : 0;
+  // slot 12 (no kernel counts there either): how the sweep's tangent kernels write a row
+  v[12] = m.path != FCG_PATH_STRUCTURED ? FCG_SWEEP_ROWS_NA
+                                        : (m.sweep_defer ? FCG_SWEEP_ROWS_DEFERRED : FCG_SWEEP_ROWS_DIRECT);
   for (int i = 0; i < n && i < 16; ++i) out[i] = v[i];
   return m.stamps ? 16 : 0;
 }

@@ -403,7 +403,6 @@ bool build_structured_plan(const fcg_desc* d, const std::vector<int32_t>& rownod
   P.nbr_pos.assign(nrn * 27, 0xFFFF);
   std::string err;
   std::mutex err_m;
-  std::atomic<int64_t> unordered{0};
   parallel_for(nrn, [&](int64_t r) {
     const int64_t p = npos[rownodes[r]];
     const int64_t i = p % NXn, jj = (p / NXn) % NYn, k = p / (NXn * NYn);
@@ -445,20 +444,7 @@ bool build_structured_plan(const fcg_desc* d, const std::vector<int32_t>& rownod
       std::lock_guard<std::mutex> lk(err_m);
       err = "row holds columns beyond the lattice neighbours";
     }
-    // lattice order (GridGenerator numbering): the lower plane's triples open the row
-    int lo_max = -1, hi_min = 1 << 30;
-    for (int t = 0; t < 27; ++t)
-    {
-      const int q = P.nbr_pos[r * 27 + t];
-      if (q == 0xFFFF) continue;
-      if (t < 9)
-        lo_max = std::max(lo_max, q);
-      else
-        hi_min = std::min(hi_min, q);
-    }
-    if (lo_max > hi_min) unordered.fetch_add(1, std::memory_order_relaxed);
   });
-  P.rows_unordered = unordered.load();
   if (!err.empty())
   {
     why = err;

@@ -89,7 +89,6 @@ struct StructHost {
   std::vector<double> lat_x;        // node coordinates on the column-node lattice
   std::vector<int32_t> lat_dof;     // column LID of the node's first DOF, -1 = none
   std::vector<uint32_t> plane_rec;  // [tiles_y][tiles_x][NK][PLANE_REC_WORDS]
-  int64_t rows_unordered = 0;       // rows whose lower-plane neighbours are not their first columns
   // Regular lattice tiles (classify_regular_tiles): a (tile, node plane) whose 16 columns are
   // owned rows of 81 entries with the context's one neighbour-position pattern reg_pos, row0
   // advancing by 3 and base by 243 along each of the tile's four y-rows.  Its compact record:

@@ -112,7 +112,10 @@ struct DeviceMesh {
   int32_t tiles_x = 0, tiles_y = 0, tiles_z = 0, seg_planes = 0;
   int32_t I0 = 0, J0 = 0, K0 = 0, NI = 0, NJ = 0, NK = 0;  // owned-node lattice box
   int32_t EX0 = 0, EY0 = 0, EZ0 = 0, EX = 0, EY = 0, EZ = 0;  // column-element lattice box
-  bool sweep_defer = false;         // rows not in lattice order: sweep MODE 3 (fcg_sweep.hip)
+  bool sweep_defer = false;         // linear kinematics: sweep MODE 3, whole rows in one layer (fcg_sweep.hip)
+  // the linear structural sweep leaves out the layers that hold no element (below and above the
+  // element box); FCG_SWEEP_SKIP_EMPTY=0 at fcg_create runs them as every other layer
+  bool sweep_skip_empty = true;
   // the reference-geometry checks, taken once at create (sweep_geometry_pass): the worst code, the
   // lowest rejected column element and whether some evaluated element has fac < 0 at a Gauss point.
   // sweep_checked: the evaluates launch the kernels that repeat these checks (something was found,

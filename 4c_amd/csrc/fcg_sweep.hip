@@ -14,18 +14,28 @@
 //                K_AB = lambda G + mu G^T + mu H + geo I
 //      (= B_a^T C B_b + K_geo of calc_lib.hpp:872-927 for the isotropic C of fill_cmat) and
 //      writes the 3 x 3 block straight into its 3 CSR rows -- or keeps the lower-layer part of
-//      an in-plane block (dz = 0) in registers until the next layer adds the upper part.
+//      an in-plane block (dz = 0) in LDS until the next layer adds the upper part.
 //      The residual rows f_A = sum fac F S N_XYZ_A (calc_lib.hpp:851-860) are summed the same way,
 //      16 lanes per column.
 // Every entry of an owned row is written exactly once, by one lane, in a fixed summation order:
-// no atomics, no row image in LDS, bitwise reproducible.  Owned-rows-only assembly and column
+// no atomics, no row image in LDS, bitwise reproducible.
+// The linear tangent (K + r, the headline; MODE 3 below) writes a row within one layer.  The 9
+// blocks of plane P's row with the plane below (dz = -1) are finished in layer P-1, the other 18
+// in layer P; on a lattice-numbered mesh they are the row's first 216 of 648 bytes, and written as
+// they finish they leave two cache lines per row half-filled in L2 for a layer, which then go to
+// memory twice (1.18 x the K bytes written at 1M elements).  So a dz = -1 block waits one layer
+// in LDS (hold_lo), its lane swapping it for the next one, and leaves beside the row's other
+// blocks: 1.03 x.  On regular lattice tiles (REGK below) all of it is addressed in closed form.
+// Layers without elements -- below the element box, on the top node plane -- are left out.
+// TotLag, the TSI passes and the internal-force kernels write blocks as they finish (MODE 0).
+// Owned-rows-only assembly and column
 // positions follow SparseMatrix::assemble (4C_linalg_sparsematrix.cpp:474-543, positions resolved
 // per node row by fcg_create), the residual LinAlg::assemble (4C_linalg_utils_sparse_algebra_assemble.cpp:72-92).
 //
 // Linear kinematics: f_int = K u exactly (E = B u, f = sum fac B^T C B u), so the residual rows are
 // summed from the finished blocks, f_A += K_AB u_B, and stage A needs neither strains nor stresses.
 //
-// Latency hiding: two workgroups per CU for linear kinematics (LDS 59 KB), one for TotLag
+// Latency hiding: two workgroups per CU for linear kinematics (LDS 59 KB, 70 KB with hold_lo), one for TotLag
 // (85 KB), plus, inside a workgroup, register prefetch of the next node plane (coordinates,
 // displacements) and plane record while the current layer computes.
 #include <hip/hip_runtime.h>
@@ -91,6 +101,7 @@ struct SweepArgs {
   int32_t tiles_x, tiles_y, seg_planes;
   int32_t I0, J0, K0, NI, NJ, NK;
   int32_t EX0, EY0, EZ0, EX, EY, EZ;  // element box; the node lattice box is EX+1 x EY+1 x EZ+1
+  int32_t skip_empty;  // linear structural passes: leave out the layers without elements
 };
 
 // node data per lattice column: X | u, and for TSI v | T
@@ -152,7 +163,7 @@ struct SweepShared {
   // it read without a branch (see emit).
   alignas(16) double hold[TX * TY + (TSI ? 0 : 1)][9][TSI ? (TH ? 9 : 18) : kHs];
 #endif
-  // DEFER (rows not in lattice order): the blocks of node plane L+1's rows with the plane below
+  // DEFER (the linear tangent kernels): the blocks of node plane L+1's rows with the plane below
   // (dz = -1, finished in layer L) wait here and are written in layer L+1 beside the row's other
   // blocks, so that each row's cache lines are filled within one layer.  Slot (column, t) belongs
   // to the one lane that emits block t of that column every layer: it reads the held block
@@ -600,10 +611,11 @@ __device__ inline void block_k(const StVK& m, const double* acc, double* Kb)
 // MODE 0: structure (K, f_int); 1: fused TSI (K_SS, k_ST, k_TS, k_TT, f_S, f_T in one pass);
 // 2: the thermal-only pass that follows a MODE-0 linear sweep (k_ST, k_TS, k_TT, f_T, and
 // k_ST (T - T_0) added into f_S) -- 8 accumulators per block instead of 16, no K stores;
-// 3: structure with the lower-plane blocks deferred one layer (hold_lo), for meshes whose CSR
-// rows do not list the lattice neighbours plane by plane (input-file numbering): a row's 27
-// triples then land all over its 648 bytes, and writing them in two layers' halves left its
-// lines half-written in L2 between the two (1.4x the K bytes written on the renumbered 1M box);
+// 3: structure with the lower-plane blocks deferred one layer (hold_lo): the linear tangent
+// kernel.  Written in two layers' parts a row leaves lines half-written in L2 between the two:
+// 1.18x the K bytes written on the lattice-numbered 1M box (the lines at a row's start and at its
+// byte 216), 1.4x on the renumbered one, whose rows do not list the lattice neighbours plane by
+// plane (input-file numbering: a row's 27 triples land all over its 648 bytes);
 // 4: the create-time geometry pass (sweep_geometry_pass): the loop's loads of the reference
 // coordinates and the element lattice and stage A's checks, no u, no visit stage, no stores.
 // CHECKED = false (structural passes of a context whose geometry pass found nothing): stage A
@@ -637,7 +649,7 @@ __global__ __launch_bounds__(256, KIN ? 1 : FCG_SWEEP_WGS) void sweep_h8_kernel(
   const int kz1 = min(kz0 + A.seg_planes, A.K0 + A.NK);
   const uint32_t* prec_tile = A.plane_rec + (int64_t(ty) * A.tiles_x + tx) * A.NK * PLANE_REC_WORDS;
   const int64_t LX = A.EX + 1, LY = A.EY + 1;
-  // Regular layers (REGK: the unchecked linear MODE-0 kernels).  fcg_create has found, per tile,
+  // Regular layers (REGK: the unchecked linear MODE-0 and MODE-3 kernels).  fcg_create has found, per tile,
   // a run of node planes whose rows all have 81 entries, one pattern of neighbour positions and
   // rows / bases in arithmetic progression along a tile row, with all 25 elements of every layer
   // between them present (classify_regular_tiles).  The layers rlo <= L < rhi of this workgroup
@@ -646,7 +658,7 @@ __global__ __launch_bounds__(256, KIN ? 1 : FCG_SWEEP_WGS) void sweep_h8_kernel(
   // branch; their element ids are not loaded; and a plane both of whose layers are regular is
   // loaded as its compact record (12 words instead of 288), put where the full record holds the
   // same words.  All of it is workgroup-uniform (scalar compares).
-  constexpr bool REGK = MODE == 0 && KIN == 0 && !CHECKED;
+  constexpr bool REGK = (MODE == 0 || MODE == 3) && KIN == 0 && !CHECKED;
   int rlo = 0, rhi = 0;
   const uint32_t* creg_tile = nullptr;
   if constexpr (REGK)
@@ -761,26 +773,39 @@ __global__ __launch_bounds__(256, KIN ? 1 : FCG_SWEEP_WGS) void sweep_h8_kernel(
     rp_s = A.reg_pos[(vis1 >> 11) & 31] + 243 * cx;
   }
 
-  // --- prologue: node planes kz0-1, kz0 and their records; prefetch plane kz0+1
+  // Layers without elements (the linear structural passes; workgroup-uniform scalar compares, and
+  // never true at a rank's interior face, whose ghost layer holds elements):
+  // * the bottom segment's first layer, K0 - 1, lies below the element box.  Its sums are +0 (a
+  //   missing element stores exact zeros, and every sum starts from the constant +0), it writes
+  //   nothing (wl is false, and no row of plane K0 has a neighbour below) and what it holds equals
+  //   the prologue's zeros: the sweep starts one layer later, at L0;
+  // * the top segment's last layer lies on the top node plane: no stage A and no visits, the emits
+  //   run on the zero accumulators (the held in-plane parts and plane L's f rows are due).
+  constexpr bool SKIPE = KIN == 0 && !TSI && !GEOM;
+  const bool skip_e = SKIPE && A.skip_empty != 0;
+  const int L0 = (skip_e && kz0 - 1 < A.EZ0) ? kz0 : kz0 - 1;
+  // --- prologue: node planes L0, L0+1 and their records; prefetch plane L0+2
 #pragma unroll
   for (int j = 0; j < NLD; ++j)
     if (n_lane[j])
     {
-      sh.node[ring(kz0 - 1)][ncol[j]][ncomp[j]] = load_node(j, kz0 - 1);
-      sh.node[ring(kz0)][ncol[j]][ncomp[j]] = load_node(j, kz0);
+      sh.node[ring(L0)][ncol[j]][ncomp[j]] = load_node(j, L0);
+      sh.node[ring(L0 + 1)][ncol[j]][ncomp[j]] = load_node(j, L0 + 1);
     }
   {
     uint32_t w[2];
-    load_rec(kz0 - 1, w);
-    store_rec(kz0 - 1, w);
-    load_rec(kz0, w);
-    store_rec(kz0, w);
+    load_rec(L0, w);
+    store_rec(L0, w);
+    load_rec(L0 + 1, w);
+    store_rec(L0 + 1, w);
   }
   int32_t dof_nxt[NLD];  // DOF of plane L+2's node-load items at the top of layer L
 #pragma unroll
-  for (int j = 0; j < NLD; ++j) dof_nxt[j] = n_lane[j] ? load_dof(j, kz0 + 1) : -1;
-  int e_cur = load_elem(kz0 - 1);
+  for (int j = 0; j < NLD; ++j) dof_nxt[j] = n_lane[j] ? load_dof(j, L0 + 2) : -1;
+  int e_cur = load_elem(L0);
   for (int v = tid; v < int(sizeof(sh.hold) / sizeof(double)); v += 256) (&sh.hold[0][0][0])[v] = 0.0;
+  if constexpr (DEFER)
+    for (int v = tid; v < int(sizeof(sh.hold_lo) / sizeof(double)); v += 256) (&sh.hold_lo[0][0][0])[v] = 0.0;
   double fkeep[NF];  // lane k = 8: D-side residual part of plane L+1's rows
 #pragma unroll
   for (int d = 0; d < NF; ++d) fkeep[d] = 0.0;
@@ -789,8 +814,9 @@ __global__ __launch_bounds__(256, KIN ? 1 : FCG_SWEEP_WGS) void sweep_h8_kernel(
   __builtin_amdgcn_s_waitcnt(0);
   __syncthreads();
 
-  for (int L = kz0 - 1; L < kz1; ++L)
+  for (int L = L0; L < kz1; ++L)
   {
+    const bool empty_top = skip_e && L >= A.EZ0 + A.EZ;  // no element in this layer (see L0)
     // issue the loads of plane L+2 (values, record), plane L+3's DOFs and layer L+1's element
     const int e_nxt = load_elem(L + 1);
     double node_nxt[NLD];
@@ -817,7 +843,7 @@ __global__ __launch_bounds__(256, KIN ? 1 : FCG_SWEEP_WGS) void sweep_h8_kernel(
     // timing probe only (wrong results): no element stage
     if (a_lane && e_cur == -12345) sweep_stage_a<KIN, TSI, CHECKED, GEOM>(sh, A, s, g, sx, sy, L, e_cur);
 #else
-    if (a_lane) sweep_stage_a<KIN, TSI, CHECKED, GEOM>(sh, A, s, g, sx, sy, L, e_cur);
+    if (a_lane && !empty_top) sweep_stage_a<KIN, TSI, CHECKED, GEOM>(sh, A, s, g, sx, sy, L, e_cur);
 #endif
     __syncthreads();
     FCG_STAMP(0);
@@ -848,7 +874,7 @@ __global__ __launch_bounds__(256, KIN ? 1 : FCG_SWEEP_WGS) void sweep_h8_kernel(
 
     // B. visit stage
     const bool wl = L >= kz0, wl1 = L + 1 < kz1;
-    constexpr bool kRingSel = !TSI && !DEFER;
+    constexpr bool kRingSel = !TSI && (!DEFER || KIN == 0);
     const int rL = ring(L), rL1 = ring(L + 1);
     const uint32_t* recL = sh.prec[rL];
     const uint32_t* recL1 = sh.prec[rL1];
@@ -876,7 +902,7 @@ __global__ __launch_bounds__(256, KIN ? 1 : FCG_SWEEP_WGS) void sweep_h8_kernel(
       // them: one LDS round trip.  emit_finish does the rest.  The two blocks that end a layer
       // (the second visit's and the self block) load together ahead of either's work, so that the
       // pair exposes one round trip, not two (see the end of the visit stage).
-      constexpr bool kBranchFree = !TSI && !DEFER && !kProbeWg3;
+      constexpr bool kBranchFree = !TSI && (!DEFER || KIN == 0) && !kProbeWg3;
       struct EmitIn {
         int32_t row0, len32;
         uint32_t base_lo, base_hi;
@@ -887,7 +913,8 @@ __global__ __launch_bounds__(256, KIN ? 1 : FCG_SWEEP_WGS) void sweep_h8_kernel(
         double held[9];
       };
       auto emit_load = [&](int act, int t, EmitIn& in) {
-        const uint32_t* rec = act == kActWriteL1 ? recL1 : recL;
+        // (DEFER: a lower-plane block is written one layer later, into plane L's row)
+        const uint32_t* rec = (act == kActWriteL1 && !DEFER) ? recL1 : recL;
         if constexpr (REG)
         {
           // the base of the tile row's first column: the one record field a regular emit reads
@@ -922,15 +949,19 @@ __global__ __launch_bounds__(256, KIN ? 1 : FCG_SWEEP_WGS) void sweep_h8_kernel(
           // every other lane the zeros of the spare column (Kb + 0 is Kb but for the sign of a
           // zero; the D side's sum is not used).  No branch around the reads, no select or copy
           // behind them.
+          // DEFER: a lower-plane block (t < 9) swaps with its slot of hold_lo the same way -- the
+          // lane reads the block held since the previous layer and stores this layer's
+          const bool lo = DEFER && act == kActWriteL1;
           in.h = sh.hold[c][(act == kActHold || act == kActWriteLHold) ? t - 9 : 0];
-          const double* hr = act == kActWriteLHold ? in.h : sh.hold[TX * TY][0];
+          if constexpr (DEFER) in.h = lo ? sh.hold_lo[c][t] : in.h;
+          const double* hr = (act == kActWriteLHold || lo) ? in.h : sh.hold[TX * TY][0];
 #pragma unroll
           for (int i = 0; i < 9; ++i) in.held[i] = hr[i];
         }
       };
       // rp: the block's entry offset in a regular layer (rp_a / rp_b / rp_s)
       auto emit_finish = [&](int act, int t, const EmitIn& in, int32_t rp, double* Kb, double* Tv) {
-        const bool to_l1 = act == kActWriteL1;
+        const bool to_l1 = act == kActWriteL1 && !DEFER;
         const int32_t row0 = in.row0, len32 = in.len32;
         const uint32_t base_lo = in.base_lo, base_hi = in.base_hi;
         const uint16_t pos = in.pos;
@@ -958,13 +989,17 @@ __global__ __launch_bounds__(256, KIN ? 1 : FCG_SWEEP_WGS) void sweep_h8_kernel(
         {
           // (the caller has put a compiler barrier between the reads and this write: all reads
           // issue before any write, and the LDS executes a wavefront's operations in order)
-          if (act == kActHold)
+          const bool lo = DEFER && act == kActWriteL1;
+          if (act == kActHold || lo)
           {
 #pragma unroll
             for (int i = 0; i < 9; ++i) in.h[i] = Kb[i];
           }
+          // (DEFER: the held lower-plane block leaves as it is, bit for bit -- it belongs to plane
+          // L's row, and the fields emit_load has read are plane L's; in a regular layer plane L's
+          // row is a regular row, whichever path the layer that held the block took)
 #pragma unroll
-          for (int i = 0; i < 9; ++i) Kb[i] = in.held[i] + Kb[i];
+          for (int i = 0; i < 9; ++i) Kb[i] = lo ? in.held[i] : in.held[i] + Kb[i];
         }
         else
         if (act == kActHold || act == kActWriteLHold)
@@ -1000,16 +1035,13 @@ __global__ __launch_bounds__(256, KIN ? 1 : FCG_SWEEP_WGS) void sweep_h8_kernel(
           }
         }
         if (act == kActHold || !WANT_K) return;
-        if constexpr (DEFER)
+        if constexpr (DEFER && !kBranchFree)
         {
           if (act == kActWriteL1)
           {
-            // the block held since the previous layer belongs to plane L's row: write it now,
-            // beside that row's other blocks; hold this layer's block for plane L+1
-            const int32_t row0L = int32_t(recL[PR_ROW0 + c]);
-            const uint16_t posL = reinterpret_cast<const uint16_t*>(recL + PR_NPOS)[27 * c + t];
-            const uint32_t bloL = recL[PR_BASE + 2 * c], bhiL = recL[PR_BASE + 2 * c + 1];
-            const int64_t lenL = int32_t(recL[PR_LEN + c]);
+            // (TotLag: no branch-free hold) the block held since the previous layer belongs to
+            // plane L's row: it is written now, beside that row's other blocks and by the same
+            // stores (the fields emit_load has read are plane L's); this layer's block waits
             double* h = sh.hold_lo[c][t];
             double old[9];
 #pragma unroll
@@ -1017,19 +1049,8 @@ __global__ __launch_bounds__(256, KIN ? 1 : FCG_SWEEP_WGS) void sweep_h8_kernel(
             __asm__ volatile("" ::: "memory");
 #pragma unroll
             for (int i = 0; i < 9; ++i) h[i] = Kb[i];
-            if (!wl || row0L < 0 || posL == 0xFFFF) return;
-            double* dlo = A.K + (int64_t(bloL) | (int64_t(bhiL) << 32)) + posL;
 #pragma unroll
-            for (int r = 0; r < 3; ++r)
-#pragma unroll
-              for (int qq = 0; qq < 3; ++qq)
-              {
-                if (OVERWRITE)
-                  dlo[r * lenL + qq] = old[3 * r + qq];
-                else
-                  dlo[r * lenL + qq] += old[3 * r + qq];
-              }
-            return;
+            for (int i = 0; i < 9; ++i) Kb[i] = old[i];
           }
         }
         // (a regular layer lies inside the write range, its rows are owned and hold all 27 blocks)
@@ -1164,7 +1185,9 @@ __global__ __launch_bounds__(256, KIN ? 1 : FCG_SWEEP_WGS) void sweep_h8_kernel(
 #endif
       constexpr int kVisitUnroll = (FCG_SWEEP_VISIT_UNROLL) ? 2 : 1;
       // unrolled: the second visit's block waits for the self block, and the two load together
-      constexpr bool kPairEmits = kVisitUnroll == 2 && kBranchFree;
+      // (not in the deferred kernels: paired, the unchecked one spills 4 VGPRs at 256 and measured
+      // slower than unpaired, profiles/sweep_rows/headline_ab.txt)
+      constexpr bool kPairEmits = kVisitUnroll == 2 && kBranchFree && !DEFER;
       double Kb2[9];
 #pragma unroll kVisitUnroll
       for (int v = 0; v < 2; ++v)
@@ -1178,15 +1201,20 @@ __global__ __launch_bounds__(256, KIN ? 1 : FCG_SWEEP_WGS) void sweep_h8_kernel(
           // keeps a basic block of its own, as under the checked kernel's mask branch.  Inlined
           // into the surrounding block it costs spills (10-16 VGPRs on the headline kernel, 150
           // and more on MODE 3 and TotLag); so placed it frees 9 (253 -> 244).  One s_cmp and
-          // one s_cbranch per visit, no LDS read behind it.
-          uint32_t always = 0u;
-          __asm__ volatile("" : "+s"(always));
-          if (always == 0u) sweep_visit<KIN, false, TSI, TH>(sh, slot, a, b1, b2, 0u, acc1, acc2);
+          // one s_cbranch per visit, no LDS read behind it.  The one case in which it is not taken:
+          // a layer without elements, whose accumulators stay +0.
+          uint32_t skipv = SKIPE ? uint32_t(__builtin_amdgcn_readfirstlane(empty_top ? 1 : 0)) : 0u;
+          __asm__ volatile("" : "+s"(skipv));
+          if (skipv == 0u) sweep_visit<KIN, false, TSI, TH>(sh, slot, a, b1, b2, 0u, acc1, acc2);
         }
         else
         {
           const uint32_t nm = TSI ? sh.neg[slot] : (v == 0 ? nm_pre[0] : nm_pre[1]);
-          if (nm == 0u)
+          if (empty_top)
+          {
+            // (a layer without elements: the accumulators stay +0)
+          }
+          else if (nm == 0u)
             sweep_visit<KIN, false, TSI, TH>(sh, slot, a, b1, b2, nm, acc1, acc2);
           else
             sweep_visit<KIN, true, TSI, TH>(sh, slot, a, b1, b2, nm, acc1, acc2);
@@ -1382,6 +1410,7 @@ SweepArgs sweep_args(const DeviceMesh& m, const double* d_u_col, double* d_K, do
   a.seg_planes = m.seg_planes;
   a.I0 = m.I0; a.J0 = m.J0; a.K0 = m.K0; a.NI = m.NI; a.NJ = m.NJ; a.NK = m.NK;
   a.EX0 = m.EX0; a.EY0 = m.EY0; a.EZ0 = m.EZ0; a.EX = m.EX; a.EY = m.EY; a.EZ = m.EZ;
+  a.skip_empty = m.sweep_skip_empty ? 1 : 0;
   return a;
 }
 }  // namespace

@@ -1070,11 +1070,23 @@ class Evaluator:
         lib().fcg_get_diagnostics(self._h, buf, 16)
         return self.SWEEP_KERNELS[int(buf[15])]
 
+    SWEEP_ROWS = ("not applicable", "direct", "deferred")
+
+    def sweep_rows(self):
+        """How the structured sweep's tangent kernels write a row (slot 12 of
+        fcg_get_diagnostics): "direct" -- the blocks with the plane below in the layer that
+        finishes them, the rest one layer later -- or "deferred": the whole row within one layer
+        (rows not in lattice order, or FCG_SWEEP_DEFER=1 at creation); "not applicable" on the
+        other paths."""
+        buf = (ctypes.c_uint64 * 16)()
+        lib().fcg_get_diagnostics(self._h, buf, 16)
+        return self.SWEEP_ROWS[int(buf[12])]
+
     def sweep_regular_layers(self):
         """(regular, total): the (tile, layer) pairs of the structured sweep that take the
         regular-tile path -- closed-form row bookkeeping, decided at fcg_create -- and all of them
         (slots 13, 14 of fcg_get_diagnostics).  regular is 0 for a context whose kernels keep
-        the plane records (TotLag, rows not in lattice order, the checked kernels) and with
+        the plane records (TotLag, rows in no arithmetic progression, the checked kernels) and with
         FCG_SWEEP_REGULAR=0 at creation; (0, 0) on the other paths."""
         buf = (ctypes.c_uint64 * 16)()
         lib().fcg_get_diagnostics(self._h, buf, 16)

@@ -238,10 +238,18 @@ int fcg_measure_hbm(int device, double* copy_gbs, double* write_gbs);
  * structured sweep that take the regular-tile path (closed-form row bookkeeping for tiles whose
  * rows fcg_create found to be 81 entries long with one neighbour pattern and rows and bases in
  * arithmetic progression; the unchecked linear kernels only, none with FCG_SWEEP_REGULAR=0 at
- * fcg_create), and all pairs the sweep's workgroups run; both 0 on every other path. */
+ * fcg_create), and all pairs the sweep's workgroups run; both 0 on every other path.
+ * out[12], always filled as well: how the structured sweep's tangent kernels write a row's blocks
+ * -- FCG_SWEEP_ROWS_DIRECT: the blocks with the plane below in the layer that finishes them, the
+ * others one layer later; FCG_SWEEP_ROWS_DEFERRED: all of a row within one layer (the lower-plane
+ * blocks wait in LDS; rows not in lattice order, or FCG_SWEEP_DEFER=1 at fcg_create);
+ * FCG_SWEEP_ROWS_NA on every other path. */
 #define FCG_SWEEP_KERNEL_NA 0
 #define FCG_SWEEP_KERNEL_CHECKED 1
 #define FCG_SWEEP_KERNEL_UNCHECKED 2
+#define FCG_SWEEP_ROWS_NA 0
+#define FCG_SWEEP_ROWS_DIRECT 1
+#define FCG_SWEEP_ROWS_DEFERRED 2
 int fcg_get_diagnostics(const fcg_ctx* ctx, uint64_t* out, int n);
 
 /* Wall time (seconds) of fcg_create's phases, the setup counterpart of 4C's FillComplete and
