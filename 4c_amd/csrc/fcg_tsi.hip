@@ -137,9 +137,10 @@ __global__ __launch_bounds__(64) void tsi_element_kernel(TsiElementArgs A)
         else if (!(det > 0)) atomicMax(&sh.bad, int(FCG_ERR_NODAL_DETJ));
         continue;
       }
-      // the thermo element throws for det < 1e-16 (4C_thermo_ele_impl.cpp:2663-2664)
+      // the thermo element throws for det < 1e-16 in both of its actions
+      // (eval_shape_func_and_derivs_at_int_point, 4C_thermo_ele_impl.cpp:2663-2664)
       if (det == 0.0) atomicMax(&sh.bad, int(FCG_ERR_SINGULAR));
-      else if (want_t && det < 1e-16) atomicMax(&sh.bad, int(FCG_ERR_NODAL_DETJ));
+      else if ((want_t || want_ts) && det < 1e-16) atomicMax(&sh.bad, int(FCG_ERR_NODAL_DETJ));
       const double fac = det * wgp[g];
       double Tg = 0.0, tr = 0.0, g0 = 0.0, g1 = 0.0, g2 = 0.0;
       for (int c = 0; c < NPE; ++c)
@@ -912,12 +913,10 @@ int fcg_tsi_evaluate_fused(fcg_ctx* sctx, fcg_tsi_ctx* ctx, int mode, const doub
     t.T0 = d.T0;
     t.conduct = d.conduct;
     t.kts = -timefac * timefac_d;  // linear_coupled_tang (4C_thermo_ele_impl.cpp:1189)
-    // the structural sweep + a thermal-only pass (default), or the one fused pass
-    static const bool split = [] {
-      const char* e = std::getenv("FCG_TSI_SPLIT");
-      return !(e && e[0] == '0');
-    }();
-    t.split = split;
+    // the structural sweep + a thermal-only pass (default), or the one fused pass; read at
+    // every call (the call synchronises anyway)
+    const char* split_env = std::getenv("FCG_TSI_SPLIT");
+    t.split = !(split_env && split_env[0] == '0');
     he = fcg::launch_sweep_h8_tsi(m, d_u_col, mode == FCG_OVERWRITE, d_Kss, d_fs_row, t, s);
   }
   int32_t errv[2] = {0, INT32_MAX};

@@ -747,7 +747,8 @@ const char* fcg_tsi_last_error(const fcg_tsi_ctx* ctx);
  *   mode      applies to k_ST, k_TS, k_TT and f_T (OVERWRITE = zero + assemble); f_S always `+=`
  *             (its mechanical part comes from fcg_evaluate_device)
  * Error codes as fcg_evaluate_device (FCG_ERR_NODAL_DETJ also for the thermo element's
- * det J < 1e-16, 4C_thermo_ele_impl.cpp:2663-2664).
+ * det J < 1e-16, 4C_thermo_ele_impl.cpp:2663-2664, which both thermo actions check:
+ * FCG_TSI_THERMO_FINTCOND and FCG_TSI_COUPLTANG, alone or together).
  */
 int fcg_tsi_evaluate_device(fcg_tsi_ctx* ctx, int parts, int mode, const double* d_v_col,
     const double* d_T_col, double timefac, double timefac_d, double* d_fs_row, double* d_Kst,
@@ -766,6 +767,8 @@ int fcg_tsi_evaluate_device(fcg_tsi_ctx* ctx, int parts, int mode, const double*
  *   mode   applies to all outputs (f_S is the full residual: K u + thermal stress part)
  * Returns FCG_ERR_ARG (last_error says why) when the contexts do not qualify; the first call
  * with a structural context checks mesh and graph identity on the device.
+ * Environment, read at every call: FCG_TSI_SPLIT=0 runs the one fused pass; unset or anything
+ * else (the default) the structural sweep followed by a thermal-only pass of the same kernel.
  */
 int fcg_tsi_evaluate_fused(fcg_ctx* sctx, fcg_tsi_ctx* ctx, int mode, const double* d_u_col,
     const double* d_v_col, const double* d_T_col, double timefac, double timefac_d,
