@@ -12,8 +12,9 @@ the BASELINE configs the hierarchy is known in advance, so it is built geometric
             gives a non-nested level: trilinear interpolation at general weights)
 
 Coarse operators are rediscretised: linear-elastic StVK hex8 assembled by the library's own
-evaluate (for affine boxes and linear kinematics this is exactly the Galerkin product P^T K P,
-the quadrature being exact for the trilinear subspace).  Transfers are the nodal interpolation of
+evaluate (for affine boxes and linear kinematics this is the Galerkin product P^T K P to the
+rounding of the Gauss rule's constants, the quadrature being exact for the trilinear subspace:
+tests/test_multigrid_ref.py).  Transfers are the nodal interpolation of
 a trilinear field (weights 1 or 1/2 per direction) and its transpose, applied by
 fcg_node_transfer.  Smoother: Chebyshev polynomial in D^-1 K with D the 3x3 nodal diagonal blocks
 (Ifpack2's Chebyshev with point-block diagonal, boost 1.1 as Ifpack2's; eigenvalue ratio 10 instead of
@@ -179,6 +180,24 @@ def box_stencil(mesh, youngs, poisson, device, dbc_rows):
         clamped[idx[full]] = 1
     return (nx, ny, nz, torch.from_numpy(row_of).to(device), torch.from_numpy(clamped).to(device),
             torch.from_numpy(S.ravel()).to(device))
+
+
+def coarse_intervals(iv, hex27, min_intervals, max_levels):
+    """Interval counts of the hex8 coarse levels below a fine box of `iv` intervals: the same
+    elements first if the fine level is hex27, then halved (odd counts to (n + 1) / 2, a non-nested
+    level with general interpolation weights) while every count stays >= min_intervals, the halving
+    still changes a count (min_intervals=1: (1 + 1) // 2 == 1) and max_levels is not reached."""
+    meshes = []
+    if hex27:
+        meshes.append(tuple(iv))
+    n = list(iv)
+    while len(meshes) + 1 < max_levels and all((v + 1) // 2 >= min_intervals for v in n):
+        half = [(v + 1) // 2 for v in n]
+        if half == n:
+            break
+        n = half
+        meshes.append(tuple(n))
+    return meshes
 
 
 class _Transfer:
@@ -682,14 +701,7 @@ class Multigrid(CycleFCG):
         if box is None or getattr(fine_mesh, "nranks", 1) != 1:
             raise ValueError("Multigrid needs a single-rank GridGenerator box (fcg.BoxMesh)")
         iv = [int(box.interval[d]) for d in range(3)]
-        meshes = []  # intervals of the hex8 coarse levels
-        if fine_mesh.celltype == fcg.HEX27:
-            meshes.append(tuple(iv))
-        n = list(iv)
-        # halve (odd counts to (n + 1) / 2, a non-nested level with general interpolation weights)
-        while len(meshes) + 1 < max_levels and all((v + 1) // 2 >= min_intervals for v in n):
-            n = [(v + 1) // 2 for v in n]
-            meshes.append(tuple(n))
+        meshes = coarse_intervals(iv, fine_mesh.celltype == fcg.HEX27, min_intervals, max_levels)
         if not meshes:
             raise ValueError(f"no coarse level for intervals {iv}: hex8 boxes need (n + 1) / 2 >= "
                              f"min_intervals ({min_intervals})")
