@@ -447,7 +447,8 @@ int fcg_tsi_destroy(fcg_tsi_ctx* ctx)
   fcg::TsiDevice& d = ctx->d;
   void* ptrs[] = {d.ele_nodes, d.ele_gid, d.node_x, d.dof_col_s, d.dof_col_t, d.inc_of, d.inc_ptr,
       d.rn_srow, d.rn_trow, d.pos_st, d.pos_ts, d.pos_tt, d.rowptr_st, d.rowptr_ts, d.rowptr_tt,
-      d.tables, d.scratch, d.err, d.col_tt, d.krylov_work};
+      d.tables, d.scratch, d.err, d.col_tt, d.krylov_work, d.cols_tt == d.col_tt ? nullptr : d.cols_tt,
+      d.inc_ele, d.inc_loc, d.ele_capa};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
@@ -701,6 +702,13 @@ int fcg_tsi_create(const fcg_tsi_desc* D, fcg_tsi_ctx** out)
   chk(upload<double>(&d.scratch, nullptr, n_inc * fcg::tsi_rec(npe), bytes));
   chk(upload<int32_t>(&d.err, nullptr, 2, bytes));
   if (fusable) chk(upload(&d.col_tt, D->col_tt, d.nnz_tt, bytes));
+  // the one-step-theta pass walks the k_TT rows of any context
+  if (fusable)
+    d.cols_tt = d.col_tt;
+  else
+    chk(upload(&d.cols_tt, D->col_tt, d.nnz_tt, bytes));
+  for (int64_t t = 0; t < D->n_rows_t; ++t)
+    d.max_row_tt = std::max(d.max_row_tt, int(D->rowptr_tt[t + 1] - D->rowptr_tt[t]));
   if (he != hipSuccess)
   {
     set_tsi_create_error(std::string("HIP allocation/copy failed: ") + hipGetErrorString(he));

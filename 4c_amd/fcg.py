@@ -146,7 +146,7 @@ EXPORTS = ["fcg_create", "fcg_destroy", "fcg_last_error", "fcg_evaluate", "fcg_e
            "fcg_neumann_surface", "fcg_neumann_volume",
            "fcg_graph_build_device", "fcg_get_graph",
            "fcg_tsi_create", "fcg_tsi_destroy", "fcg_tsi_last_error", "fcg_tsi_evaluate_device",
-           "fcg_tsi_evaluate_fused",
+           "fcg_tsi_evaluate_fused", "fcg_tsi_capacity", "fcg_tsi_ost_combine",
            "fcg_box_mesh_create", "fcg_box_mesh_destroy", "fcg_box_mesh_desc", "fcg_box_mesh_maps",
            "fcg_box_mesh_counts", "fcg_box_mesh_create_ex", "fcg_box_mesh_owned_rows",
            "fcg_comm_unique_id", "fcg_comm_create", "fcg_comm_destroy", "fcg_comm_size", "fcg_comm_rank", "fcg_comm_allreduce",
@@ -292,6 +292,8 @@ def lib():
                                           ctypes.c_double, vp, vp, vp, vp, vp, vp, _i32p]
     L.fcg_tsi_evaluate_fused.argtypes = [vp, vp, ctypes.c_int, vp, vp, vp, ctypes.c_double,
                                          ctypes.c_double, vp, vp, vp, vp, vp, vp, vp, _i32p]
+    L.fcg_tsi_capacity.argtypes = [vp, ctypes.c_double, _dp, ctypes.c_int, vp, vp, _i32p]
+    L.fcg_tsi_ost_combine.argtypes = [vp, ctypes.c_double, ctypes.c_double, vp, vp, vp, vp, vp, vp, vp]
     i64, c_int, c_dbl = ctypes.c_int64, ctypes.c_int, ctypes.c_double
     L.fcg_amg_aggregate.argtypes = [i64, vp, vp, vp, vp]
     L.fcg_amg_aggregate.restype = i64
@@ -1262,6 +1264,40 @@ class TsiEvaluator:
         if rc != 0:
             raise FcgError(rc, lib().fcg_tsi_last_error(self._h).decode(), bad.value)
 
+    def capacity(self, capa, ele_capa=None, mode=OVERWRITE, out=None, stream=None):
+        """fcg_tsi_capacity: the capacity matrix of the thermo elements (MAT_Fourier CAPA) on the
+        k_TT graph into `out` ([nnz_tt] device tensor; None: a new one, which ACCUMULATE starts
+        from zeros).  ele_capa: one capacity per column element (host array), `capa` is then
+        ignored.  Returns the tensor; the call waits for the stream."""
+        import torch
+        if out is None:
+            out = torch.empty(int(self.graph.nnz_tt), dtype=torch.float64,
+                              device=torch.device("cuda", self.device))
+            if mode == ACCUMULATE:
+                out.zero_()
+        cp = None
+        if ele_capa is not None:
+            ec = np.ascontiguousarray(ele_capa, dtype=np.float64).reshape(-1)
+            if ec.size != self.mesh.n_ele:
+                raise ValueError(f"ele_capa has {ec.size} entries, the context {self.mesh.n_ele} elements")
+            cp = _np_ptr(ec, _dp)
+        bad = ctypes.c_int32(-1)
+        rc = lib().fcg_tsi_capacity(self._h, float(capa), cp, int(mode), _tensor_ptr(out),
+                                    _torch_stream(stream, self.device), ctypes.byref(bad))
+        if rc != 0:
+            raise FcgError(rc, lib().fcg_tsi_last_error(self._h).decode(), bad.value)
+        return out
+
+    def ost_combine(self, theta, dt, C, T, Tn, h=None, Ktt=None, fT=None, stream=None):
+        """fcg_tsi_ost_combine: Ktt <- C/dt + theta Ktt and fT <- theta fT + C (T - Tn)/dt + h in one
+        pass over the owned thermo rows (asynchronous).  Ktt / fT hold the FINTCOND evaluate at T
+        on entry; either may be None (residual only / tangent only), h None is 0."""
+        rc = lib().fcg_tsi_ost_combine(self._h, float(theta), float(dt), _tensor_ptr(C),
+                                       _tensor_ptr(T), _tensor_ptr(Tn), _tensor_ptr(h),
+                                       _tensor_ptr(Ktt), _tensor_ptr(fT),
+                                       _torch_stream(stream, self.device))
+        if rc != 0:
+            self._fail(rc)
 
     def _fail(self, rc):
         raise FcgError(rc, lib().fcg_tsi_last_error(self._h).decode())

@@ -1,14 +1,22 @@
-"""Static monolithic thermo-structure interaction with every vector and matrix resident in HBM:
+"""Monolithic thermo-structure interaction (static, or with a transient thermal field) with every
+vector and matrix resident in HBM:
 the Newton loop of TSI::Monolithic (4C_tsi_monolithic.cpp: newton_full, setup_system_matrix,
 linear_solve) around the library's TSI evaluates, Dirichlet applies and the FGMRES solve of the
 non-symmetric block system [[K_SS, K_ST], [K_TS, K_TT]] (fcg_tsi_gmres_solve).
 
-Both fields are statics with linear kinematics (what fcg_tsi_evaluate_* covers): per time step the
-loads are taken at t_{n+1}; per Newton iteration the velocity of the quasi-static structure is
+By default both fields are statics with linear kinematics (what fcg_tsi_evaluate_* covers): per
+time step the loads are taken at t_{n+1}; per Newton iteration the velocity of the quasi-static structure is
 v = (d - d_n) / dt (TSI::Algorithm::calc_velocity), the blocks are evaluated with timefac 1 and
 timefac_d 1 / dt, r = f_int - f_ext, the Dirichlet rows are applied to all four blocks and both
 residuals, the increment solves K dx = -r and x += dx.  The iteration stops when
-|dx| <= tol_inc max(1, |x|) on the stacked vector."""
+|dx| <= tol_inc max(1, |x|) on the stacked vector.
+
+thermal="ost": the thermal field is transient (THERMAL DYNAMIC / DYNAMICTYPE OneStepTheta beside the
+quasi-static structure at t_{n+1}).  The evaluates run with timefac theta and timefac_d 1 / dt, so K_TS
+arrives theta-weighted; fcg_tsi_ost_combine turns K_TT into C/dt + theta K_TT and f_T into
+C (T - T_n)/dt + theta f_T + h with h = (1 - theta)(f_int,n - f_ext,n) - theta f_ext,n+1 formed once per
+step (thermo.OneStepTheta; f_int,0 is evaluated at (T_0, v = 0), f_int,n after every step at the
+accepted state).  K_ST, K_SS and f_S are those of the static case."""
 
 import torch
 
@@ -31,7 +39,7 @@ class TsiMonolithic:
 
     def __init__(self, struct_ev, tsi_ev, dt, fext_s, fext_t, dbc_s, dbc_t, T_init=None, fused=None,
                  tol_inc=1e-13, max_iter=30, lin_rtol=1e-10, restart=50, lin_max_iter=2000,
-                 precond="bgs", amg=None, amg_t=None):
+                 precond="bgs", amg=None, amg_t=None, thermal="statics", capa=None, theta=1.0):
         self.sev, self.tev, self.dt = struct_ev, tsi_ev, float(dt)
         self.dev = torch.device("cuda", struct_ev.device)
         g = tsi_ev.graph
@@ -59,6 +67,19 @@ class TsiMonolithic:
         self.Kts, self.Ktt = z(g.nnz_ts), z(g.nnz_tt)
         self.step_no, self.t = 0, 0.0
         self.history = []
+        if thermal not in ("statics", "ost"):
+            raise ValueError('TsiMonolithic: thermal is "statics" or "ost"')
+        self.ost = thermal == "ost"
+        self.timefac = 1.0
+        if self.ost:
+            if capa is None:
+                raise ValueError('TsiMonolithic: thermal="ost" needs the heat capacity capa')
+            self.theta = self.timefac = float(theta)
+            self.C = tsi_ev.capacity(capa)
+            self.T_n, self.h = z(self.nt), z(self.nt)
+            self.fint_n = z(self.nt)
+            self._fint_n()  # at (T_0, v = 0)
+            self.fext_n = self._load(self.fext_t, 0.0).clone()
 
     def _vec(self, a):
         return torch.as_tensor(a).to(device=self.dev, dtype=torch.float64).contiguous()
@@ -66,10 +87,15 @@ class TsiMonolithic:
     def _load(self, f, t):
         return self._vec(f(t) if callable(f) else f)
 
+    def _fint_n(self):
+        """f_int,n = f_T at the current (v, T); K_TT is scratch here, every iteration overwrites it."""
+        self.tev.evaluate_device(fcg.TSI_THERMO_FINTCOND, fcg.OVERWRITE, self.v, self.T, fT=self.fint_n,
+                                 Ktt=self.Ktt)
+
     def _evaluate(self):
         if self.fused is not False:
             try:
-                self.tev.evaluate_fused(self.sev, fcg.OVERWRITE, self.d, self.v, self.T, 1.0,
+                self.tev.evaluate_fused(self.sev, fcg.OVERWRITE, self.d, self.v, self.T, self.timefac,
                                         1.0 / self.dt, fs=self.fs, Kss=self.Kss, Kst=self.Kst,
                                         fT=self.fT, Ktt=self.Ktt, Kts=self.Kts)
                 self.fused = True
@@ -79,7 +105,7 @@ class TsiMonolithic:
                     raise
                 self.fused = False  # the contexts do not qualify: two evaluates from now on
         self.sev.evaluate_device(fcg.CALC_NLNSTIFF, fcg.OVERWRITE, self.d, self.fs, self.Kss)
-        self.tev.evaluate_device(fcg.TSI_ALL, fcg.OVERWRITE, self.v, self.T, 1.0, 1.0 / self.dt,
+        self.tev.evaluate_device(fcg.TSI_ALL, fcg.OVERWRITE, self.v, self.T, self.timefac, 1.0 / self.dt,
                                  fs=self.fs, Kst=self.Kst, fT=self.fT, Ktt=self.Ktt, Kts=self.Kts)
 
     def step(self):
@@ -87,6 +113,10 @@ class TsiMonolithic:
         self.t = self.step_no * self.dt
         fes, fet = self._load(self.fext_s, self.t), self._load(self.fext_t, self.t)
         self.d_n.copy_(self.d)
+        if self.ost:
+            torch.sub(self.fint_n, self.fext_n, out=self.h)
+            self.h.mul_(1.0 - self.theta).sub_(fet, alpha=self.theta)
+            self.T_n.copy_(self.T)
         rec = {"step": self.step_no, "iterations": 0, "gmres_iterations": [], "gmres_rel_residual": []}
         for it in range(self.max_iter):
             torch.sub(self.d, self.d_n, out=self.v)
@@ -94,7 +124,12 @@ class TsiMonolithic:
             self._evaluate()
             # b = -(f_int - f_ext), zero on the Dirichlet rows
             self.fs.sub_(fes).neg_()
-            self.fT.sub_(fet).neg_()
+            if self.ost:
+                self.tev.ost_combine(self.theta, self.dt, self.C, self.T, self.T_n, h=self.h, Ktt=self.Ktt,
+                                     fT=self.fT)
+                self.fT.neg_()
+            else:
+                self.fT.sub_(fet).neg_()
             self.sev.dirichlet_apply(self.dbc_s, self.Kss, self.fs)
             self.tev.dirichlet_apply(self.dbc_s, self.dbc_t, self.Kst, self.Kts, self.Ktt, self.fT)
             if self.amg is not None:
@@ -121,6 +156,11 @@ class TsiMonolithic:
         else:
             self.history.append(rec)
             raise RuntimeError(f"TSI Newton did not converge in step {self.step_no}")
+        if self.ost:
+            torch.sub(self.d, self.d_n, out=self.v)
+            self.v.div_(self.dt)
+            self._fint_n()
+            self.fext_n = fet.clone()
         self.history.append(rec)
         return rec
 

@@ -814,6 +814,43 @@ int fcg_tsi_gmres_solve(fcg_ctx* sctx, fcg_tsi_ctx* tctx, fcg_amg* amg_s_or_null
     const fcg_gmres_options* opt, int* iterations, double* rel_residual, void* stream);
 
 /*
+ * The transient thermal field (fcg_thermo.hip): 4C's THERMAL DYNAMIC / DYNAMICTYPE OneStepTheta
+ * on the thermo context.  Both calls work on the k_TT graph of any context fcg_tsi_create accepts
+ * (hex8 and hex27, any numbering, ranked contexts: owned rows, ghost elements contribute, columns
+ * in the thermo column map).
+ *
+ * fcg_tsi_capacity: the capacity matrix C_ab = sum_e sum_g capa_e w_g det J_g N_a N_b of the thermo
+ * element (MAT_Fourier CAPA, the volumetric heat capacity), with the Gauss rule of
+ * FCG_TSI_THERMO_FINTCOND and J from the reference coordinates.  capa > 0, or a host table
+ * ele_capa[n_ele] of positive entries (column-element order); anything else: FCG_ERR_ARG, and
+ * fcg_tsi_last_error names the entry.  OVERWRITE writes every owned entry (entries that belong to
+ * no element pair become 0), ACCUMULATE adds.  det J < 1e-16 at a Gauss point (the check of
+ * FCG_TSI_THERMO_FINTCOND): FCG_ERR_NODAL_DETJ with the lowest failing element GID.  One wavefront
+ * per owned node sums the node's elements in ascending column-element order in LDS: no atomics on
+ * doubles, two calls give the same bits.  A per-context plan (5 bytes per incidence, and the
+ * staging copy of ele_capa) is built on the first call and counted in the context's device memory:
+ * calls on one context must not run concurrently.  Blocking, like fcg_mass_assemble.
+ *
+ * fcg_tsi_ost_combine: one pass over the owned thermo rows per Newton iteration.  On entry d_Ktt
+ * and d_fT_row hold what FCG_TSI_THERMO_FINTCOND produced at T_{n+1}; on return
+ *   K_TT[j] = fma(theta, K_TT[j], C[j] / dt)                            tangent  C/dt + theta K_TT
+ *   f_T[i]  = theta f_T[i] + (1/dt) sum_j C_ij (T_j - Tn_j) + h_i       residual
+ * (Thermo::TimIntOneStepTheta: r = C (T_{n+1} - T_n)/dt + theta (F_int,n+1 - F_ext,n+1) +
+ * (1 - theta)(F_int,n - F_ext,n), with h = (1 - theta)(f_int,n - f_ext,n) - theta f_ext,n+1 the
+ * caller's step-constant vector, NULL = 0).  The difference T_j - Tn_j is formed before the product
+ * with C_ij, as the element's ecapa (T_{n+1} - T_n).  d_T_col / d_Tn_col: thermo column map.
+ * d_Ktt NULL: residual only; d_fT_row NULL: tangent only; both NULL, theta outside (0, 1], or dt
+ * not finite or <= 0: FCG_ERR_ARG.  4 / 16 / 64 lanes per row by the longest row, partial sums in
+ * a fixed lane order: deterministic.  Asynchronous on `stream`, like fcg_spmv; a context without
+ * rows returns FCG_OK before it looks at its pointers.
+ */
+int fcg_tsi_capacity(fcg_tsi_ctx* ctx, double capa, const double* ele_capa /* host [n_ele] or NULL */,
+    int mode /* fcg_mode */, double* d_Ctt /* [nnz_tt] */, void* stream, int32_t* bad_ele_gid);
+int fcg_tsi_ost_combine(fcg_tsi_ctx* ctx, double theta, double dt, const double* d_Ctt,
+    const double* d_T_col, const double* d_Tn_col, const double* d_h_row /* may be NULL */,
+    double* d_Ktt /* in/out, may be NULL */, double* d_fT_row /* in/out, may be NULL */, void* stream);
+
+/*
  * Scalar smoothed-aggregation AMG of K_TT (fcg_samg_plan.cpp, fcg_samg.hip): the multigrid of the
  * thermal block, one DOF per node, the constant as near-null space -- what MueLu builds for the
  * thermal field of 4C's TSI block preconditioners, and a solver for a conduction problem on its
