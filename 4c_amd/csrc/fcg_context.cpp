@@ -16,6 +16,7 @@
 #include "fcg_internal.hpp"
 #include "fcg_status.hpp"
 #include "fcg_shape.hpp"
+#include "fcg_upload.hpp"
 
 namespace {
 
@@ -30,17 +31,7 @@ void set_create_error(const std::string& s)
   g_create_error = s;
 }
 
-template <class T>
-hipError_t upload(T** dst, const T* src, int64_t n, int64_t& bytes)
-{
-  *dst = nullptr;
-  if (n == 0) return hipSuccess;
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(dst), sizeof(T) * n);
-  if (e != hipSuccess) return e;
-  bytes += sizeof(T) * n;
-  if (src) return hipMemcpy(*dst, src, sizeof(T) * n, hipMemcpyHostToDevice);
-  return hipSuccess;
-}
+using fcg::upload;
 
 void free_mesh(fcg::DeviceMesh& m)
 {

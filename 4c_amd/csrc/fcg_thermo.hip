@@ -11,7 +11,8 @@
 //            tang = C/dt + theta K_TT; the element forms ecapa (T_{n+1} - T_n), never C T - C T_n
 //
 // Kernels: capacity_kernel (one wavefront per owned node: per incidence of the node, in ascending
-// column-element order, lane g forms det J and capa w det J N_a at Gauss point g, lane b sums over
+// column-element order -- its element and local node are the context's inc_ele / inc_loc, uploaded
+// by fcg_tsi_create from the host plan -- lane g forms det J and capa w det J N_a at Gauss point g, lane b sums over
 // g in Gauss-point order and adds into the node's row image in LDS; the row is written once) and
 // ost_combine_kernel (4 / 16 / 64 lanes per owned thermo row: K <- fma(theta, K, C/dt) and the row
 // sum C (T - T_n) in one walk of the row).  Owned rows only, no atomics on doubles, bitwise
@@ -35,21 +36,6 @@ namespace {
 constexpr int kOstBlock = 256;
 
 int thermo_grid(int64_t work, int cap) { return int(work < cap ? (work > 0 ? work : 1) : cap); }
-
-// inc_of [n_ele][npe] -> (column element, local node) of every incidence
-__global__ __launch_bounds__(256) void capacity_plan_kernel(int64_t n_ele, int npe,
-    const int32_t* __restrict__ inc_of, int32_t* __restrict__ inc_ele, uint8_t* __restrict__ inc_loc)
-{
-  const int64_t n = n_ele * npe;
-  for (int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += int64_t(gridDim.x) * blockDim.x)
-  {
-    const int32_t q = inc_of[i];
-    if (q < 0) continue;
-    const int64_t e = i / npe;
-    inc_ele[q] = int32_t(e);
-    inc_loc[q] = uint8_t(i - e * npe);
-  }
-}
 
 struct CapacityArgs {
   int64_t n_rownodes;
@@ -182,35 +168,6 @@ __global__ __launch_bounds__(kOstBlock) void ost_combine_kernel(int64_t n, const
   if (tail) f[i] = fma(theta, fi, inv_dt * a) + hi;
 }
 
-// the capacity plan of the context: built once, counted in device_bytes
-hipError_t capacity_plan(fcg_tsi_ctx* ctx, hipStream_t s)
-{
-  TsiDevice& d = ctx->d;
-  if (d.inc_ele || d.n_inc == 0) return hipSuccess;
-  int32_t* ie = nullptr;
-  uint8_t* il = nullptr;
-  hipError_t he = hipMalloc(reinterpret_cast<void**>(&ie), sizeof(int32_t) * d.n_inc);
-  if (he == hipSuccess) he = hipMalloc(reinterpret_cast<void**>(&il), size_t(d.n_inc));
-  if (he == hipSuccess)
-  {
-    const int64_t work = (d.n_ele * d.npe + 255) / 256;
-    hipLaunchKernelGGL(capacity_plan_kernel, dim3(thermo_grid(work, 4096)), dim3(256), 0, s, d.n_ele, d.npe,
-        d.inc_of, ie, il);
-    he = hipGetLastError();
-  }
-  if (he == hipSuccess) he = hipStreamSynchronize(s);
-  if (he != hipSuccess)
-  {
-    if (ie) (void)hipFree(ie);
-    if (il) (void)hipFree(il);
-    return he;
-  }
-  d.inc_ele = ie;
-  d.inc_loc = il;
-  ctx->device_bytes += int64_t(sizeof(int32_t) + 1) * d.n_inc;
-  return hipSuccess;
-}
-
 }  // namespace
 }  // namespace fcg
 
@@ -245,8 +202,8 @@ int fcg_tsi_capacity(fcg_tsi_ctx* ctx, double capa, const double* ele_capa, int 
   if (d.n_rownodes == 0) return FCG_OK;
   (void)hipSetDevice(ctx->device);
   hipStream_t s = stream_ptr ? static_cast<hipStream_t>(stream_ptr) : ctx->stream;
-  hipError_t he = fcg::capacity_plan(ctx, s);
-  if (he == hipSuccess && ele_capa && d.n_ele > 0)
+  hipError_t he = hipSuccess;
+  if (ele_capa && d.n_ele > 0)
   {
     if (!d.ele_capa)
     {

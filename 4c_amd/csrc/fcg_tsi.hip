@@ -28,6 +28,10 @@
 // tsi_assemble_kernel (one wavefront per owned node: its 3 k_ST rows, its k_TS row and its k_TT row
 // are summed in element order in an LDS row image and written once, coalesced).  Owned rows only,
 // no atomics, bitwise reproducible -- the contract of the structural path.
+//
+// fcg_tsi_create is the driver of the context's creation: the host stages of fcg_tsi_plan.cpp
+// (descriptor checks, node rows, row layout, incidences, positions, tables, node consistency,
+// constants), then the context (device, stream) and the upload of what the stages filled.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -43,8 +47,9 @@
 #include "fcg_hex8_element.hpp"
 #include "fcg_internal.hpp"
 #include "fcg_status.hpp"
-#include "fcg_shape.hpp"
 #include "fcg_tsi_internal.hpp"
+#include "fcg_tsi_plan.hpp"
+#include "fcg_upload.hpp"
 
 namespace fcg {
 namespace {
@@ -361,18 +366,6 @@ __global__ __launch_bounds__(64) void tsi_assemble_kernel(TsiAssembleArgs A)
   }
 }
 
-template <class T>
-hipError_t upload(T** dst, const T* src, int64_t n, int64_t& bytes)
-{
-  *dst = nullptr;
-  if (n <= 0) return hipSuccess;
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(dst), sizeof(T) * n);
-  if (e != hipSuccess) return e;
-  bytes += int64_t(sizeof(T)) * n;
-  if (src) return hipMemcpy(*dst, src, sizeof(T) * n, hipMemcpyHostToDevice);
-  return hipMemset(*dst, 0, sizeof(T) * n);
-}
-
 // The structural context of a fused call describes the same mesh with the node graph of the TSI
 // context: same elements, node coordinates and column DOFs, K rows = the 3 x 3 expansion of the k_TT rows.
 struct FusedCheckArgs {
@@ -428,6 +421,97 @@ void set_tsi_create_error(const std::string& s)
 
 int grid_for(int64_t work, int cap) { return int(work < cap ? (work > 0 ? work : 1) : cap); }
 
+namespace plan = tsi_plan;  // the host stages of fcg_tsi_create (fcg_tsi_plan.cpp)
+
+int open_tsi_context(const fcg_tsi_desc* D, fcg_tsi_ctx*& ctx, std::string& why)
+{
+  ctx = new fcg_tsi_ctx();
+  ctx->device = D->device;
+  hipError_t he = hipSetDevice(D->device);
+  if (he == hipSuccess) he = hipStreamCreateWithFlags(&ctx->stream, hipStreamDefault);  // ordered with the null stream (torch's default)
+  if (he != hipSuccess)
+  {
+    why = std::string("HIP: ") + hipGetErrorString(he);
+    delete ctx;
+    ctx = nullptr;
+    return fcg_device_error();
+  }
+  return FCG_OK;
+}
+
+// sizes, constants and flags of the context, from the descriptor and the plan
+void fill_tsi_device(TsiDevice& d, const fcg_tsi_desc* D, const plan::NodeRows& N, const plan::Incidences& I,
+    const plan::Constants& C, bool node_consistent, int max_row_tt)
+{
+  d.npe = plan::npe_of(D);
+  d.n_ele = D->n_ele;
+  d.n_node = D->n_node;
+  d.n_rownodes = N.nrn();
+  d.n_inc = I.n_inc;
+  d.n_rows_s = D->n_rows_s;
+  d.n_cols_s = D->n_cols_s;
+  d.n_rows_t = D->n_rows_t;
+  d.n_cols_t = D->n_cols_t;
+  d.nnz_st = C.nnz_st;
+  d.nnz_ts = C.nnz_ts;
+  d.nnz_tt = C.nnz_tt;
+  d.m = C.m;
+  d.lambda = C.lambda;
+  d.mu = C.mu;
+  d.node_consistent = node_consistent;
+  d.fusable = node_consistent && d.npe == 8;
+  d.T0 = D->inittemp;
+  d.conduct = D->conduct;
+  d.max_row_tt = max_row_tt;
+}
+
+// the descriptor's arrays and the plan's tables; the first error wins, the later calls still run,
+// and device_bytes counts what was allocated
+hipError_t upload_tsi(fcg_tsi_ctx* ctx, const fcg_tsi_desc* D, const plan::NodeRows& N,
+    const plan::Incidences& I, const plan::Constants& C, const std::vector<double>& tab)
+{
+  TsiDevice& d = ctx->d;
+  const int npe = d.npe;
+  const int64_t nrn = d.n_rownodes, n_inc = d.n_inc;
+  int64_t& bytes = ctx->device_bytes;
+  hipError_t he = hipSuccess;
+  auto chk = [&](hipError_t x) {
+    if (he == hipSuccess) he = x;
+  };
+  chk(upload(&d.ele_nodes, D->ele_nodes, D->n_ele * npe, bytes));
+  chk(upload(&d.ele_gid, D->ele_gid ? D->ele_gid : C.ele_gid.data(), D->n_ele, bytes));
+  chk(upload(&d.node_x, D->node_x, D->n_node * 3, bytes));
+  chk(upload(&d.dof_col_s, D->node_dof_col_s, D->n_node, bytes));
+  chk(upload(&d.dof_col_t, D->node_dof_col_t, D->n_node, bytes));
+  chk(upload(&d.inc_of, I.inc_of.data(), D->n_ele * npe, bytes));
+  chk(upload(&d.inc_ptr, I.inc_ptr.data(), nrn + 1, bytes));
+  chk(upload(&d.rn_srow, N.srow.data(), nrn, bytes));
+  chk(upload(&d.rn_trow, N.trow.data(), nrn, bytes));
+  chk(upload(&d.pos_st, I.pos_st.data(), n_inc * npe, bytes));
+  chk(upload(&d.pos_ts, I.pos_ts.data(), n_inc * npe, bytes));
+  chk(upload(&d.pos_tt, I.pos_tt.data(), n_inc * npe, bytes));
+  chk(upload(&d.rowptr_st, D->rowptr_st, D->n_rows_s + 1, bytes));
+  chk(upload(&d.rowptr_ts, D->rowptr_ts, D->n_rows_t + 1, bytes));
+  chk(upload(&d.rowptr_tt, D->rowptr_tt, D->n_rows_t + 1, bytes));
+  chk(upload(&d.tables, tab.data(), int64_t(tab.size()), bytes));
+  // scratch and the error words start as zeros
+  const int64_t n_scratch = n_inc * tsi_rec(npe);
+  chk(upload<double>(&d.scratch, nullptr, n_scratch, bytes));
+  if (d.scratch) chk(hipMemset(d.scratch, 0, sizeof(double) * n_scratch));
+  chk(upload<int32_t>(&d.err, nullptr, 2, bytes));
+  if (d.err) chk(hipMemset(d.err, 0, sizeof(int32_t) * 2));
+  if (d.node_consistent) chk(upload(&d.col_tt, D->col_tt, d.nnz_tt, bytes));
+  // the one-step-theta pass walks the k_TT rows of any context
+  if (d.node_consistent)
+    d.cols_tt = d.col_tt;
+  else
+    chk(upload(&d.cols_tt, D->col_tt, d.nnz_tt, bytes));
+  // the capacity kernel's view of an incidence: its column element and local node
+  chk(upload(&d.inc_ele, I.inc_ele.data(), n_inc, bytes));
+  chk(upload(&d.inc_loc, I.inc_loc.data(), n_inc, bytes));
+  return he;
+}
+
 }  // namespace
 }  // namespace fcg
 
@@ -456,262 +540,39 @@ int fcg_tsi_destroy(fcg_tsi_ctx* ctx)
   return FCG_OK;
 }
 
+// The stages of a TSI context's creation, in order; the host ones are fcg_tsi_plan.cpp's.  Every
+// FCG_ERR_ARG is found before the first device call (open_tsi_context).
 int fcg_tsi_create(const fcg_tsi_desc* D, fcg_tsi_ctx** out)
 {
-  using fcg::set_tsi_create_error;
+  namespace plan = fcg::tsi_plan;
   if (!D || !out) return FCG_ERR_ARG;
   *out = nullptr;
-  if (D->abi_version != FCG_ABI_VERSION)
-  {
-    set_tsi_create_error("abi_version mismatch");
-    return FCG_ERR_ARG;
-  }
-  if (D->celltype != FCG_HEX8 && D->celltype != FCG_HEX27)
-  {
-    set_tsi_create_error("unsupported celltype");
-    return FCG_ERR_ARG;
-  }
-  // Mat::PAR::ThermoStVenantKirchhoff (4C_mat_thermostvenantkirchhoff.cpp:35-36)
-  if (!(D->youngs > 0.0) || D->poisson >= 0.5 || D->poisson < -1.0)
-  {
-    set_tsi_create_error("Poisson's ratio must be in [-1;0.5) and Young's modulus > 0");
-    return FCG_ERR_ARG;
-  }
-  const int npe = D->celltype == FCG_HEX27 ? 27 : 8;
-  const int maxn = npe == 8 ? 27 : 125;
-  if (D->n_ele < 0 || D->n_node < 0 || D->n_ele >= (int64_t(1) << 31) ||
-      (D->n_ele > 0 && (!D->ele_nodes || !D->node_x || !D->node_dof_col_s || !D->node_dof_col_t ||
-                           !D->node_dof_row_s || !D->node_dof_row_t)) ||
-      (D->n_rows_s > 0 && (!D->rowptr_st || !D->col_st)) ||
-      (D->n_rows_t > 0 && (!D->rowptr_ts || !D->col_ts || !D->rowptr_tt || !D->col_tt)))
-  {
-    set_tsi_create_error("invalid descriptor arrays/sizes");
-    return FCG_ERR_ARG;
-  }
-  for (int64_t i = 0; i < D->n_ele * npe; ++i)
-    if (D->ele_nodes[i] < 0 || D->ele_nodes[i] >= D->n_node)
-    {
-      set_tsi_create_error("element references a node outside [0, n_node)");
-      return FCG_ERR_ARG;
-    }
-  // owned nodes: the structural rows and the thermo row are owned together
-  std::vector<int32_t> rownodes;
-  for (int64_t n = 0; n < D->n_node; ++n)
-  {
-    const int32_t rs = D->node_dof_row_s[n], rt = D->node_dof_row_t[n];
-    const int32_t cs = D->node_dof_col_s[n], ct = D->node_dof_col_t[n];
-    if ((rs >= 0) != (rt >= 0) || cs < 0 || cs + 3 > D->n_cols_s || ct < 0 || ct >= D->n_cols_t ||
-        rs + 3 > D->n_rows_s || rt >= D->n_rows_t)
-    {
-      set_tsi_create_error("node DOF maps out of range, or a node owned in one field only");
-      return FCG_ERR_ARG;
-    }
-    if (rs >= 0) rownodes.push_back(int32_t(n));
-  }
-  std::sort(rownodes.begin(), rownodes.end(),
-      [&](int32_t a, int32_t b) { return D->node_dof_row_s[a] < D->node_dof_row_s[b]; });
-  const int64_t nrn = int64_t(rownodes.size());
-  std::vector<int32_t> rn_of_node(D->n_node, -1), srow(nrn), trow(nrn);
-  for (int64_t r = 0; r < nrn; ++r)
-  {
-    rn_of_node[rownodes[r]] = int32_t(r);
-    srow[r] = D->node_dof_row_s[rownodes[r]];
-    trow[r] = D->node_dof_row_t[rownodes[r]];
-  }
-  // the 3 k_ST rows of a node share one list of at most maxn thermo columns
-  for (int64_t r = 0; r < nrn; ++r)
-  {
-    const int64_t* p = D->rowptr_st + srow[r];
-    const int64_t l = p[1] - p[0];
-    if (l > maxn || p[2] - p[1] != l || p[3] - p[2] != l ||
-        std::memcmp(D->col_st + p[0], D->col_st + p[1], sizeof(int32_t) * l) != 0 ||
-        std::memcmp(D->col_st + p[0], D->col_st + p[2], sizeof(int32_t) * l) != 0 ||
-        D->rowptr_ts[trow[r] + 1] - D->rowptr_ts[trow[r]] > 3 * maxn ||
-        D->rowptr_tt[trow[r] + 1] - D->rowptr_tt[trow[r]] > maxn)
-    {
-      set_tsi_create_error("k_ST/k_TS/k_TT rows do not have the node-graph layout");
-      return FCG_ERR_ARG;
-    }
-  }
-  // incidences grouped by owned node, element order
-  std::vector<int64_t> inc_ptr(nrn + 1, 0);
-  for (int64_t i = 0; i < D->n_ele * npe; ++i)
-  {
-    const int32_t rn = rn_of_node[D->ele_nodes[i]];
-    if (rn >= 0) inc_ptr[rn + 1]++;
-  }
-  for (int64_t r = 0; r < nrn; ++r) inc_ptr[r + 1] += inc_ptr[r];
-  const int64_t n_inc = inc_ptr[nrn];
-  if (n_inc >= (int64_t(1) << 31))
-  {
-    set_tsi_create_error("too many incidences for one context (> 2^31)");
-    return FCG_ERR_ARG;
-  }
-  std::vector<int32_t> inc_of(D->n_ele * npe, -1), inc_ele(n_inc);
-  {
-    std::vector<int64_t> fill(inc_ptr.begin(), inc_ptr.end() - 1);
-    for (int64_t e = 0; e < D->n_ele; ++e)
-      for (int a = 0; a < npe; ++a)
-      {
-        const int32_t rn = rn_of_node[D->ele_nodes[e * npe + a]];
-        if (rn < 0) continue;
-        const int64_t k = fill[rn]++;
-        inc_of[e * npe + a] = int32_t(k);
-        inc_ele[k] = int32_t(e);
-      }
-  }
-  // column positions (SparseMatrix::assemble's row search, 4C_linalg_sparsematrix.cpp:471-543,
-  // resolved once)
-  std::vector<uint16_t> pos_st(n_inc * npe), pos_ts(n_inc * npe), pos_tt(n_inc * npe);
-  for (int64_t r = 0; r < nrn; ++r)
-  {
-    const int32_t* cst = D->col_st + D->rowptr_st[srow[r]];
-    const int64_t lst = D->rowptr_st[srow[r] + 1] - D->rowptr_st[srow[r]];
-    const int32_t* cts = D->col_ts + D->rowptr_ts[trow[r]];
-    const int64_t lts = D->rowptr_ts[trow[r] + 1] - D->rowptr_ts[trow[r]];
-    const int32_t* ctt = D->col_tt + D->rowptr_tt[trow[r]];
-    const int64_t ltt = D->rowptr_tt[trow[r] + 1] - D->rowptr_tt[trow[r]];
-    for (int64_t k = inc_ptr[r]; k < inc_ptr[r + 1]; ++k)
-    {
-      const int32_t* en = D->ele_nodes + int64_t(inc_ele[k]) * npe;
-      for (int b = 0; b < npe; ++b)
-      {
-        const int32_t tc = D->node_dof_col_t[en[b]], sc = D->node_dof_col_s[en[b]];
-        const int32_t* i1 = std::lower_bound(cst, cst + lst, tc);
-        const int32_t* i2 = std::lower_bound(cts, cts + lts, sc);
-        const int32_t* i3 = std::lower_bound(ctt, ctt + ltt, tc);
-        if (i1 == cst + lst || *i1 != tc || i3 == ctt + ltt || *i3 != tc ||
-            i2 + 3 > cts + lts || i2[0] != sc || i2[1] != sc + 1 || i2[2] != sc + 2)
-        {
-          set_tsi_create_error("a TSI block graph lacks an element coupling, or a node's "
-                               "displacement columns are not contiguous");
-          return FCG_ERR_ARG;
-        }
-        pos_st[k * npe + b] = uint16_t(i1 - cst);
-        pos_ts[k * npe + b] = uint16_t(i2 - cts);
-        pos_tt[k * npe + b] = uint16_t(i3 - ctt);
-      }
-    }
-  }
-  // tables: dN at GPs | N at GPs | dN at nodes | weights (hex_8point / hex_27point: the thermo
-  // element's DisTypeToOptGaussRule, 4C_thermo_ele_impl_utils.hpp:28-50, is the solid's rule)
-  const int ct = D->celltype == FCG_HEX27 ? fcg::kHex27 : fcg::kHex8;
-  std::vector<double> tab(npe * npe * 3 * 2 + npe * npe + npe);
-  {
-    double xi[81], w[27], xn[81];
-    fcg::gauss_rule(ct, xi, w);
-    fcg::node_param_coords(ct, xn);
-    double* dNg = tab.data();
-    double* Ng = dNg + npe * npe * 3;
-    double* dNn = Ng + npe * npe;
-    double* wg = dNn + npe * npe * 3;
-    for (int g = 0; g < npe; ++g)
-    {
-      fcg::shape_deriv(ct, &xi[3 * g], dNg + 3 * npe * g);
-      fcg::shape_values(ct, &xi[3 * g], Ng + npe * g);
-      fcg::shape_deriv(ct, &xn[3 * g], dNn + 3 * npe * g);
-      wg[g] = w[g];
-    }
-  }
-
-  // node-consistent numbering (what fcg_tsi_evaluate_fused requires): thermo DOF LIDs are the
-  // structural ones / 3 and the three block graphs are expansions of one node graph (the k_TT graph)
-  // (hex8 and hex27: the block operator and its solve take both; the fused evaluate is hex8's)
-  bool fusable = D->n_rows_s == 3 * D->n_rows_t && D->n_cols_s == 3 * D->n_cols_t;
-  for (int64_t n = 0; fusable && n < D->n_node; ++n)
-    fusable = D->node_dof_col_s[n] == 3 * D->node_dof_col_t[n] &&
-              D->node_dof_row_s[n] == (D->node_dof_row_t[n] < 0 ? D->node_dof_row_s[n] : 3 * D->node_dof_row_t[n]);
-  for (int64_t t = 0; fusable && t < D->n_rows_t; ++t)
-  {
-    const int64_t b = D->rowptr_tt[t], lt = D->rowptr_tt[t + 1] - b;
-    fusable = D->rowptr_ts[t] == 3 * b && D->rowptr_ts[t + 1] - D->rowptr_ts[t] == 3 * lt;
-    for (int d = 0; fusable && d < 3; ++d)
-      fusable = D->rowptr_st[3 * t + d] == 3 * b + d * lt &&
-                std::memcmp(D->col_st + D->rowptr_st[3 * t + d], D->col_tt + b, sizeof(int32_t) * lt) == 0;
-    for (int64_t j = 0; fusable && j < 3 * lt; ++j)
-      fusable = D->col_ts[3 * b + j] == 3 * D->col_tt[b + j / 3] + int32_t(j % 3);
-  }
-  if (fusable && D->n_rows_t > 0)
-    fusable = D->rowptr_st[D->n_rows_s] == 3 * D->rowptr_tt[D->n_rows_t] &&
-              D->rowptr_ts[D->n_rows_t] == 3 * D->rowptr_tt[D->n_rows_t];
-
-  auto* ctx = new fcg_tsi_ctx();
-  ctx->device = D->device;
-  hipError_t he = hipSetDevice(D->device);
-  if (he == hipSuccess) he = hipStreamCreateWithFlags(&ctx->stream, hipStreamDefault);  // ordered with the null stream (torch's default)
-  if (he != hipSuccess)
-  {
-    set_tsi_create_error(std::string("HIP: ") + hipGetErrorString(he));
-    delete ctx;
-    return fcg_device_error();
-  }
-  fcg::TsiDevice& d = ctx->d;
-  d.npe = npe;
-  d.n_ele = D->n_ele;
-  d.n_node = D->n_node;
-  d.n_rownodes = nrn;
-  d.n_inc = n_inc;
-  d.n_rows_s = D->n_rows_s;
-  d.n_cols_s = D->n_cols_s;
-  d.n_rows_t = D->n_rows_t;
-  d.n_cols_t = D->n_cols_t;
-  d.nnz_st = D->n_rows_s ? D->rowptr_st[D->n_rows_s] : 0;
-  d.nnz_ts = D->n_rows_t ? D->rowptr_ts[D->n_rows_t] : 0;
-  d.nnz_tt = D->n_rows_t ? D->rowptr_tt[D->n_rows_t] : 0;
-  // st_modulus (4C_mat_thermostvenantkirchhoff.cpp:331-369)
-  {
-    const double c1 = D->youngs / (1.0 + D->poisson);
-    const double b1 = c1 * D->poisson / (1.0 - 2.0 * D->poisson);
-    const double mu = 0.5 * c1, lambda = b1;
-    d.m = (-1.0) * (2.0 * mu + 3.0 * lambda) * D->thexpans;
-    d.lambda = lambda;
-    d.mu = mu;
-  }
-  d.node_consistent = fusable;
-  d.fusable = fusable && npe == 8;
-  d.T0 = D->inittemp;
-  d.conduct = D->conduct;
-  std::vector<int32_t> eg;
-  if (!D->ele_gid)
-  {
-    eg.resize(D->n_ele);
-    for (int64_t e = 0; e < D->n_ele; ++e) eg[e] = int32_t(e);
-  }
-  int64_t& bytes = ctx->device_bytes;
-  he = hipSuccess;
-  auto chk = [&](hipError_t x) {
-    if (he == hipSuccess) he = x;
+  std::string why;
+  int rc = FCG_OK;
+  auto failed = [&](int code) {
+    rc = code;
+    if (rc != FCG_OK) fcg::set_tsi_create_error(why);
+    return rc != FCG_OK;
   };
-  using fcg::upload;
-  chk(upload(&d.ele_nodes, D->ele_nodes, D->n_ele * npe, bytes));
-  chk(upload(&d.ele_gid, D->ele_gid ? D->ele_gid : eg.data(), D->n_ele, bytes));
-  chk(upload(&d.node_x, D->node_x, D->n_node * 3, bytes));
-  chk(upload(&d.dof_col_s, D->node_dof_col_s, D->n_node, bytes));
-  chk(upload(&d.dof_col_t, D->node_dof_col_t, D->n_node, bytes));
-  chk(upload(&d.inc_of, inc_of.data(), D->n_ele * npe, bytes));
-  chk(upload(&d.inc_ptr, inc_ptr.data(), nrn + 1, bytes));
-  chk(upload(&d.rn_srow, srow.data(), nrn, bytes));
-  chk(upload(&d.rn_trow, trow.data(), nrn, bytes));
-  chk(upload(&d.pos_st, pos_st.data(), n_inc * npe, bytes));
-  chk(upload(&d.pos_ts, pos_ts.data(), n_inc * npe, bytes));
-  chk(upload(&d.pos_tt, pos_tt.data(), n_inc * npe, bytes));
-  chk(upload(&d.rowptr_st, D->rowptr_st, D->n_rows_s + 1, bytes));
-  chk(upload(&d.rowptr_ts, D->rowptr_ts, D->n_rows_t + 1, bytes));
-  chk(upload(&d.rowptr_tt, D->rowptr_tt, D->n_rows_t + 1, bytes));
-  chk(upload(&d.tables, tab.data(), int64_t(tab.size()), bytes));
-  chk(upload<double>(&d.scratch, nullptr, n_inc * fcg::tsi_rec(npe), bytes));
-  chk(upload<int32_t>(&d.err, nullptr, 2, bytes));
-  if (fusable) chk(upload(&d.col_tt, D->col_tt, d.nnz_tt, bytes));
-  // the one-step-theta pass walks the k_TT rows of any context
-  if (fusable)
-    d.cols_tt = d.col_tt;
-  else
-    chk(upload(&d.cols_tt, D->col_tt, d.nnz_tt, bytes));
-  for (int64_t t = 0; t < D->n_rows_t; ++t)
-    d.max_row_tt = std::max(d.max_row_tt, int(D->rowptr_tt[t + 1] - D->rowptr_tt[t]));
+  if (failed(plan::check_descriptor(D, why))) return rc;
+  plan::NodeRows rows;
+  if (failed(plan::build_node_rows(D, rows, why))) return rc;
+  if (failed(plan::check_row_layout(D, rows, why))) return rc;
+  plan::Incidences inc;
+  if (failed(plan::build_incidences(D, rows, inc, why))) return rc;
+  if (failed(plan::build_positions(D, rows, inc, why))) return rc;
+  // the rest of the host plan (no error exit)
+  const std::vector<double> tables = plan::build_tables(D->celltype);
+  const bool node_consistent = plan::node_consistent(D);
+  const plan::Constants constants = plan::build_constants(D);
+
+  fcg_tsi_ctx* ctx = nullptr;
+  if (failed(fcg::open_tsi_context(D, ctx, why))) return rc;
+  fcg::fill_tsi_device(ctx->d, D, rows, inc, constants, node_consistent, plan::max_row_tt(D));
+  const hipError_t he = fcg::upload_tsi(ctx, D, rows, inc, constants, tables);
   if (he != hipSuccess)
   {
-    set_tsi_create_error(std::string("HIP allocation/copy failed: ") + hipGetErrorString(he));
+    fcg::set_tsi_create_error(std::string("HIP allocation/copy failed: ") + hipGetErrorString(he));
     fcg_tsi_destroy(ctx);
     return fcg_device_error();
   }

@@ -1,6 +1,7 @@
-// fcg_tsi_internal.hpp -- the TSI context's layout, shared by fcg_tsi.hip (create, evaluate),
-// fcg_tsi_solve.hip (the monolithic block operator and its solve) and fcg_thermo.hip (capacity
-// matrix and one-step-theta pass).  Not part of the public ABI.
+// fcg_tsi_internal.hpp -- the TSI context's layout, shared by fcg_tsi.hip (create: the upload of
+// the host plan of fcg_tsi_plan.cpp; evaluate), fcg_tsi_solve.hip (the monolithic block operator
+// and its solve) and fcg_thermo.hip (capacity matrix and one-step-theta pass).  Not part of the
+// public ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -49,8 +50,9 @@ struct TsiDevice {
   int64_t krylov_doubles = 0;
   // the transient thermal field (fcg_thermo.hip).  cols_tt: the k_TT columns of any context (col_tt
   // itself when that is kept, else a copy of its own); max_row_tt: the longest k_TT row.  The
-  // capacity plan, built on the first fcg_tsi_capacity: the column element and the local node of
-  // every incidence, and the staging buffer of a per-element capacity table
+  // capacity kernel's plan, uploaded at create with the other tables: the column element and the
+  // local node of every incidence.  ele_capa: the staging buffer of a per-element capacity table,
+  // allocated by the first fcg_tsi_capacity that is given one
   int32_t* cols_tt = nullptr;
   int max_row_tt = 0;
   int32_t* inc_ele = nullptr;    // [n_inc]

@@ -827,9 +827,10 @@ int fcg_tsi_gmres_solve(fcg_ctx* sctx, fcg_tsi_ctx* tctx, fcg_amg* amg_s_or_null
  * no element pair become 0), ACCUMULATE adds.  det J < 1e-16 at a Gauss point (the check of
  * FCG_TSI_THERMO_FINTCOND): FCG_ERR_NODAL_DETJ with the lowest failing element GID.  One wavefront
  * per owned node sums the node's elements in ascending column-element order in LDS: no atomics on
- * doubles, two calls give the same bits.  A per-context plan (5 bytes per incidence, and the
- * staging copy of ele_capa) is built on the first call and counted in the context's device memory:
- * calls on one context must not run concurrently.  Blocking, like fcg_mass_assemble.
+ * doubles, two calls give the same bits.  The kernel's plan (5 bytes per incidence) is part of the
+ * context from fcg_tsi_create on; the staging copy of ele_capa is allocated by the first call that
+ * is given a table and counted in the context's device memory: calls on one context must not run
+ * concurrently.  Blocking, like fcg_mass_assemble.
  *
  * fcg_tsi_ost_combine: one pass over the owned thermo rows per Newton iteration.  On entry d_Ktt
  * and d_fT_row hold what FCG_TSI_THERMO_FINTCOND produced at T_{n+1}; on return
