@@ -576,6 +576,8 @@ int fcg_tsi_create(const fcg_tsi_desc* D, fcg_tsi_ctx** out)
     fcg_tsi_destroy(ctx);
     return fcg_device_error();
   }
+  ctx->h_dof_col_t.assign(D->node_dof_col_t, D->node_dof_col_t + D->n_node);
+  ctx->h_dof_row_t.assign(D->node_dof_row_t, D->node_dof_row_t + D->n_node);
   *out = ctx;
   return FCG_OK;
 }

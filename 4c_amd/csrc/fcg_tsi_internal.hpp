@@ -1,13 +1,14 @@
 // fcg_tsi_internal.hpp -- the TSI context's layout, shared by fcg_tsi.hip (create: the upload of
 // the host plan of fcg_tsi_plan.cpp; evaluate), fcg_tsi_solve.hip (the monolithic block operator
-// and its solve) and fcg_thermo.hip (capacity matrix and one-step-theta pass).  Not part of the
-// public ABI.
+// and its solve), fcg_thermo.hip (capacity matrix and one-step-theta pass) and fcg_tsi_surface.hip (thermal
+// boundary conditions).  Not part of the public ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <string>
+#include <vector>
 
 namespace fcg {
 
@@ -68,6 +69,9 @@ struct fcg_tsi_ctx {
   fcg::TsiDevice d;
   std::string last_error;
   int64_t device_bytes = 0;
+  // host copies of the descriptor's thermo maps [n_node], for the plans made after create
+  // (fcg_tsi_surface_create, fcg_tsi_surface.hip)
+  std::vector<int32_t> h_dof_col_t, h_dof_row_t;
 };
 
 // the thermo context a scalar AMG handle was created on (fcg_samg.hip)

@@ -147,6 +147,8 @@ EXPORTS = ["fcg_create", "fcg_destroy", "fcg_last_error", "fcg_evaluate", "fcg_e
            "fcg_graph_build_device", "fcg_get_graph",
            "fcg_tsi_create", "fcg_tsi_destroy", "fcg_tsi_last_error", "fcg_tsi_evaluate_device",
            "fcg_tsi_evaluate_fused", "fcg_tsi_capacity", "fcg_tsi_ost_combine",
+           "fcg_tsi_surface_create", "fcg_tsi_surface_set", "fcg_tsi_surface_info", "fcg_tsi_surface_tables",
+           "fcg_tsi_convection", "fcg_tsi_surface_flux", "fcg_tsi_surface_destroy",
            "fcg_box_mesh_create", "fcg_box_mesh_destroy", "fcg_box_mesh_desc", "fcg_box_mesh_maps",
            "fcg_box_mesh_counts", "fcg_box_mesh_create_ex", "fcg_box_mesh_owned_rows",
            "fcg_comm_unique_id", "fcg_comm_create", "fcg_comm_destroy", "fcg_comm_size", "fcg_comm_rank", "fcg_comm_allreduce",
@@ -294,6 +296,14 @@ def lib():
                                          ctypes.c_double, vp, vp, vp, vp, vp, vp, vp, _i32p]
     L.fcg_tsi_capacity.argtypes = [vp, ctypes.c_double, _dp, ctypes.c_int, vp, vp, _i32p]
     L.fcg_tsi_ost_combine.argtypes = [vp, ctypes.c_double, ctypes.c_double, vp, vp, vp, vp, vp, vp, vp]
+    L.fcg_tsi_surface_create.argtypes = [vp, ctypes.c_int64, _i32p, ctypes.POINTER(vp)]
+    L.fcg_tsi_surface_set.argtypes = [vp, ctypes.c_double, _dp, ctypes.c_double, _dp, ctypes.c_double, _dp,
+                                      _i64p]
+    L.fcg_tsi_surface_info.argtypes = [vp, _i64p, _i64p, _i64p]
+    L.fcg_tsi_surface_tables.argtypes = [vp] + [ctypes.POINTER(vp)] * 7
+    L.fcg_tsi_convection.argtypes = [vp, ctypes.c_double, ctypes.c_double, vp, vp, vp, vp]
+    L.fcg_tsi_surface_flux.argtypes = [vp, ctypes.c_double, vp, vp]
+    L.fcg_tsi_surface_destroy.argtypes = [vp]
     i64, c_int, c_dbl = ctypes.c_int64, ctypes.c_int, ctypes.c_double
     L.fcg_amg_aggregate.argtypes = [i64, vp, vp, vp, vp]
     L.fcg_amg_aggregate.restype = i64
@@ -1348,6 +1358,147 @@ class TsiEvaluator:
         if rc != 0:
             self._fail(rc)
         return it.value, rr.value
+
+
+# hex27 surface connectivity (4C_fem_general_utils_local_connectivity_matrices.hpp:51-54); the hex8
+# faces are the first four entries of each row
+HEX_SURFACES = np.array([[0, 3, 2, 1, 11, 10, 9, 8, 20], [0, 1, 5, 4, 8, 13, 16, 12, 21],
+                         [1, 2, 6, 5, 9, 14, 17, 13, 22], [2, 3, 7, 6, 10, 15, 18, 14, 23],
+                         [0, 4, 7, 3, 12, 19, 15, 11, 24], [4, 5, 6, 7, 16, 17, 18, 19, 25]])
+
+
+def boundary_faces(mesh):
+    """(face_nodes [n][4 or 9] int32, face_ele [n] int32): the faces that belong to exactly one column
+    element of `mesh` (BoxMesh or Discretization), as column node ids in 4C's surface order, ordered by
+    element and surface number; face_ele is the column element of each.  Meaningful on single-rank
+    meshes, where these are the faces of the body's boundary: on a rank of a split mesh the faces on
+    the edge of the ghost layer belong to one column element too."""
+    en = np.asarray(mesh.ele_nodes)
+    nfn = 4 if mesh.celltype == HEX8 else 9
+    faces = en[:, HEX_SURFACES[:, :nfn]].reshape(-1, nfn)
+    corners = np.sort(faces[:, :4], axis=1)
+    order = np.lexsort(corners.T[::-1])
+    sc = corners[order]
+    same = np.all(sc[1:] == sc[:-1], axis=1)
+    shared = np.zeros(len(sc), dtype=bool)
+    shared[1:] |= same
+    shared[:-1] |= same
+    keep = np.ones(len(sc), dtype=bool)
+    keep[order[shared]] = False
+    ele = np.repeat(np.arange(len(en), dtype=np.int32), 6)
+    return np.ascontiguousarray(faces[keep], dtype=np.int32), np.ascontiguousarray(ele[keep])
+
+
+class TsiSurface:
+    """A surface of a TsiEvaluator's mesh with a heat convection condition (coefficient, surrounding
+    temperature) and a heat flux (fcg_tsi_surface): 4C's DESIGN THERMO CONVECTION SURF CONDITIONS and a
+    thermal surface Neumann condition, integrated once on the device by set() and applied per Newton
+    iteration by convection() / per load evaluation by flux().  face_nodes: [n_faces][4 or 9] column
+    node ids in any valid quad4 / quad9 order (boundary_faces gives those of a whole single-rank
+    body).  Close the surface before its evaluator."""
+
+    def __init__(self, tev, face_nodes):
+        self.tev = tev
+        self.device = tev.device
+        nfn = 4 if tev.mesh.celltype == HEX8 else 9
+        fn = np.ascontiguousarray(face_nodes, dtype=np.int32)
+        if fn.size % nfn or (fn.ndim == 2 and fn.shape[1] != nfn):
+            raise ValueError(f"face_nodes: {nfn} nodes per face")
+        self.face_nodes = fn = fn.reshape(-1, nfn)
+        self.n_faces = len(fn)
+        h = ctypes.c_void_p()
+        rc = lib().fcg_tsi_surface_create(tev._h, self.n_faces, _np_ptr(fn, _i32p), ctypes.byref(h))
+        if rc != 0:
+            tev._fail(rc)
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().fcg_tsi_surface_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def info(self):
+        """dict(n_faces, n_rows, n_entries, device_bytes): surface rows, compact-row entries."""
+        a, b, c = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        lib().fcg_tsi_surface_info(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c))
+        return dict(n_faces=self.n_faces, n_rows=a.value, n_entries=b.value, device_bytes=c.value)
+
+    def _face_arg(self, v, what):
+        if np.ndim(v) == 0:
+            return float(v), None, None
+        a = np.ascontiguousarray(v, dtype=np.float64).reshape(-1)
+        if a.size != self.n_faces:
+            raise ValueError(f"{what} has {a.size} entries, the surface {self.n_faces} faces")
+        return 0.0, _np_ptr(a, _dp), a
+
+    def set(self, coeff=0.0, surtemp=0.0, flux=0.0):
+        """fcg_tsi_surface_set: heat transfer coefficient (>= 0), surrounding temperature and heat
+        flux, each a scalar or one value per face; runs the setup kernel and waits for it.  A refused
+        value raises FcgError (code 3) naming the face and leaves the earlier tables in place."""
+        c, cp, _c = self._face_arg(coeff, "coeff")
+        t, tp, _t = self._face_arg(surtemp, "surtemp")
+        q, qp, _q = self._face_arg(flux, "flux")
+        bad = ctypes.c_int64(-1)
+        rc = lib().fcg_tsi_surface_set(self._h, c, cp, t, tp, q, qp, ctypes.byref(bad))
+        if rc != 0:
+            raise FcgError(rc, lib().fcg_tsi_last_error(self.tev._h).decode(), bad.value)
+        return self
+
+    def _vec(self, t, n, what):
+        if t is None:
+            return None
+        import torch
+        if (t.dtype != torch.float64 or not t.is_cuda or t.device.index != self.device
+                or not t.is_contiguous() or t.numel() != int(n)):
+            raise ValueError(f"{what}: a contiguous float64 tensor of {int(n)} entries on cuda:{self.device}")
+        return _tensor_ptr(t)
+
+    def convection(self, T, fT=None, Ktt=None, coeff_scale=1.0, surtemp_scale=1.0, stream=None):
+        """fcg_tsi_convection: fT += s_c (A T - s_t g) on the surface rows and Ktt += s_c A at the
+        compact rows' positions, in one asynchronous pass.  T: thermo column map; fT / Ktt: the
+        outputs of the FINTCOND evaluate; either may be None."""
+        g = self.tev.graph
+        rc = lib().fcg_tsi_convection(self._h, float(coeff_scale), float(surtemp_scale),
+                                      self._vec(T, g.n_cols_t, "T"), self._vec(fT, g.n_rows_t, "fT"),
+                                      self._vec(Ktt, g.nnz_tt, "Ktt"), _torch_stream(stream, self.device))
+        if rc != 0:
+            self.tev._fail(rc)
+
+    def flux(self, f, scale=1.0, stream=None):
+        """fcg_tsi_surface_flux: f += scale q on the surface rows (asynchronous)."""
+        rc = lib().fcg_tsi_surface_flux(self._h, float(scale), self._vec(f, self.tev.graph.n_rows_t, "f"),
+                                        _torch_stream(stream, self.device))
+        if rc != 0:
+            self.tev._fail(rc)
+
+    def tables(self):
+        """Copies of the surface's device arrays as torch tensors on the device: rows [n_rows] (thermo
+        rows), ptr [n_rows + 1], col / pos / A [n_entries] (thermo column, position in the k_TT value
+        array, convection operator), g / q [n_rows]; A, g and q are what the last set() made."""
+        import torch
+        i = self.info
+        nr, ne = i["n_rows"], i["n_entries"]
+        p = [ctypes.c_void_p() for _ in range(7)]
+        lib().fcg_tsi_surface_tables(self._h, *[ctypes.byref(x) for x in p])
+        spec = (("rows", np.int32, nr), ("ptr", np.int64, nr + 1), ("col", np.int32, ne), ("pos", np.int64, ne),
+                ("A", np.float64, ne), ("g", np.float64, nr), ("q", np.float64, nr))
+        out = {}
+        dev = torch.device("cuda", self.device)
+        for (name, dt, n), ptr in zip(spec, p):
+            a = np.zeros(int(n) if nr else 0, dtype=dt)
+            if a.size:
+                rc = lib().fcg_memcpy_d2h(a.ctypes.data_as(ctypes.c_void_p), ptr, a.nbytes)
+                if rc != 0:
+                    raise FcgError(rc, "fcg_memcpy_d2h failed")
+            out[name] = torch.from_numpy(a).to(dev)
+        return out
 
 
 def graph_build_device(celltype, ele_nodes, node_dof_col, node_dof_row, n_rows, device=0,

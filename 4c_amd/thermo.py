@@ -7,7 +7,11 @@ Per time step, with h = (1 - theta)(f_int,n - f_ext,n) - theta f_ext,n+1 formed 
 tsi.TsiMonolithic's shape: evaluate K_TT and f_T at T_{n+1}, combine them to the tangent
 C/dt + theta K_TT and the residual r = C (T_{n+1} - T_n)/dt + theta f_T + h, b = -r, Dirichlet rows
 (unit rows, b = 0: prescribed temperatures keep their T_init values), solve, T += dT; stop when
-|dT| <= tol_inc max(1, |T|).  After the step f_int,n becomes f_T at the accepted state."""
+|dT| <= tol_inc max(1, |T|).  After the step f_int,n becomes f_T at the accepted state.
+
+Heat convection on surfaces (fcg.TsiSurface, 4C's Thermo::TimInt::apply_force_external_conv) is part
+of the internal force: one pass per surface right after every evaluate adds s_c(t) (A T - s_t(t) g)
+to f_T and s_c(t) A to K_TT, so theta weighs it with the rest and f_int,n carries the old one."""
 
 import ctypes
 
@@ -81,19 +85,45 @@ def jacobi_cg(csr, vals, b, x, rtol, max_iter):
     return it, torch.linalg.vector_norm(r).item() / nb
 
 
+def convection_list(convection):
+    """The drivers' `convection` argument as a list of (surface, coeff_funct, surtemp_funct): a
+    fcg.TsiSurface, a tuple (surface, coeff_funct, surtemp_funct) whose functs are callables t -> scale
+    or None (scale 1), or a list of these; None: no surface."""
+    if convection is None:
+        return []
+    if isinstance(convection, (fcg.TsiSurface, tuple)):
+        convection = [convection]
+    out = []
+    for c in convection:
+        surface, fc, ft = c if isinstance(c, tuple) else (c, None, None)
+        if not isinstance(surface, fcg.TsiSurface):
+            raise TypeError("convection: a TsiSurface or (TsiSurface, coeff_funct, surtemp_funct)")
+        out.append((surface, fc, ft))
+    return out
+
+
+def apply_convection(conv, t, T, fT=None, Ktt=None):
+    """Every surface of convection_list's `conv` with the scales of time t onto fT and Ktt."""
+    for surface, fc, ft in conv:
+        surface.convection(T, fT=fT, Ktt=Ktt, coeff_scale=1.0 if fc is None else float(fc(t)),
+                           surtemp_scale=1.0 if ft is None else float(ft(t)))
+
+
 class OneStepTheta:
     """tsi_ev: the TsiEvaluator of one single-rank mesh with node-consistent thermo numbering.
     capa: MAT_Fourier CAPA (ele_capa: one value per element instead).  fext_t: a row vector
     (tensor or array) or a callable t -> vector.  dbc_t: Dirichlet row LIDs, whose temperatures
     keep their T_init values.  amg_t: an amg.ScalarAMG of tsi_ev (set up on every tangent); None:
-    Jacobi-preconditioned conjugate gradients on the library's scalar CSR product.
+    Jacobi-preconditioned conjugate gradients on the library's scalar CSR product.  convection:
+    surfaces with a set convection condition (convection_list), applied after every evaluate with
+    the scales of the evaluate's time.
 
     step() advances one time step, run(nstep) several; `history` holds per step the Newton
     iterations and per solve the linear iterations and relative residual (the keys of
     tsi.TsiMonolithic).  Raises RuntimeError when Newton or a linear solve misses its tolerance."""
 
     def __init__(self, tsi_ev, capa, dt, theta, fext_t, dbc_t, T_init, amg_t=None, tol_inc=1e-13,
-                 max_iter=30, lin_rtol=1e-10, lin_max_iter=2000, ele_capa=None):
+                 max_iter=30, lin_rtol=1e-10, lin_max_iter=2000, ele_capa=None, convection=None):
         g = tsi_ev.graph
         if g.n_rows_t != g.n_cols_t:
             raise ValueError("OneStepTheta: single-rank thermo contexts only")
@@ -105,6 +135,7 @@ class OneStepTheta:
         self.amg_t = amg_t
         if amg_t is not None:
             amg_t.check_dirichlet(self.dbc_t.cpu().numpy())
+        self.conv = convection_list(convection)
         self.tol_inc, self.max_iter = float(tol_inc), int(max_iter)
         self.lin_rtol, self.lin_max_iter = float(lin_rtol), int(lin_max_iter)
         z = lambda n: torch.zeros(int(n), dtype=torch.float64, device=self.dev)
@@ -130,6 +161,7 @@ class OneStepTheta:
     def _fintcond(self):
         self.tev.evaluate_device(fcg.TSI_THERMO_FINTCOND, fcg.OVERWRITE, self.v, self.T, fT=self.fT,
                                  Ktt=self.Ktt)
+        apply_convection(self.conv, self.t, self.T, fT=self.fT, Ktt=self.Ktt)
 
     def heat_content(self):
         """1^T C T, the heat the body holds."""

@@ -16,11 +16,15 @@ quasi-static structure at t_{n+1}).  The evaluates run with timefac theta and ti
 arrives theta-weighted; fcg_tsi_ost_combine turns K_TT into C/dt + theta K_TT and f_T into
 C (T - T_n)/dt + theta f_T + h with h = (1 - theta)(f_int,n - f_ext,n) - theta f_ext,n+1 formed once per
 step (thermo.OneStepTheta; f_int,0 is evaluated at (T_0, v = 0), f_int,n after every step at the
-accepted state).  K_ST, K_SS and f_S are those of the static case."""
+accepted state).  K_ST, K_SS and f_S are those of the static case.
+
+Heat convection on surfaces (fcg.TsiSurface) is a separate pass after either evaluate path: it adds
+s_c(t) (A T - s_t(t) g) to f_T and s_c(t) A to K_TT before the combine, and to f_int,n."""
 
 import torch
 
 from . import fcg
+from .thermo import apply_convection, convection_list
 
 
 class TsiMonolithic:
@@ -31,7 +35,8 @@ class TsiMonolithic:
     fcg_tsi_evaluate_fused per iteration (True), two evaluates (False), or fused when the contexts
     qualify (None).  precond: "bgs" or "diag"; amg: an amg.NativeAMG of struct_ev for the
     structural block (set up on every K_SS), None: nodal block Jacobi; amg_t: an amg.ScalarAMG of
-    tsi_ev for the thermal block (set up on every K_TT), None: the diagonal of K_TT.
+    tsi_ev for the thermal block (set up on every K_TT), None: the diagonal of K_TT.  convection:
+    surfaces with a set convection condition (thermo.convection_list's forms).
 
     step() advances one time step, run(nstep) several; `history` holds per step the Newton
     iterations and per solve the GMRES iterations and relative residual.  Raises RuntimeError when
@@ -39,7 +44,8 @@ class TsiMonolithic:
 
     def __init__(self, struct_ev, tsi_ev, dt, fext_s, fext_t, dbc_s, dbc_t, T_init=None, fused=None,
                  tol_inc=1e-13, max_iter=30, lin_rtol=1e-10, restart=50, lin_max_iter=2000,
-                 precond="bgs", amg=None, amg_t=None, thermal="statics", capa=None, theta=1.0):
+                 precond="bgs", amg=None, amg_t=None, thermal="statics", capa=None, theta=1.0,
+                 convection=None):
         self.sev, self.tev, self.dt = struct_ev, tsi_ev, float(dt)
         self.dev = torch.device("cuda", struct_ev.device)
         g = tsi_ev.graph
@@ -67,6 +73,7 @@ class TsiMonolithic:
         self.Kts, self.Ktt = z(g.nnz_ts), z(g.nnz_tt)
         self.step_no, self.t = 0, 0.0
         self.history = []
+        self.conv = convection_list(convection)
         if thermal not in ("statics", "ost"):
             raise ValueError('TsiMonolithic: thermal is "statics" or "ost"')
         self.ost = thermal == "ost"
@@ -91,6 +98,7 @@ class TsiMonolithic:
         """f_int,n = f_T at the current (v, T); K_TT is scratch here, every iteration overwrites it."""
         self.tev.evaluate_device(fcg.TSI_THERMO_FINTCOND, fcg.OVERWRITE, self.v, self.T, fT=self.fint_n,
                                  Ktt=self.Ktt)
+        apply_convection(self.conv, self.t, self.T, fT=self.fint_n)
 
     def _evaluate(self):
         if self.fused is not False:
@@ -122,6 +130,7 @@ class TsiMonolithic:
             torch.sub(self.d, self.d_n, out=self.v)
             self.v.div_(self.dt)
             self._evaluate()
+            apply_convection(self.conv, self.t, self.T, fT=self.fT, Ktt=self.Ktt)
             # b = -(f_int - f_ext), zero on the Dirichlet rows
             self.fs.sub_(fes).neg_()
             if self.ost:

@@ -852,6 +852,62 @@ int fcg_tsi_ost_combine(fcg_tsi_ctx* ctx, double theta, double dt, const double*
     double* d_Ktt /* in/out, may be NULL */, double* d_fT_row /* in/out, may be NULL */, void* stream);
 
 /*
+ * Thermal boundary conditions on the thermo context (fcg_tsi_surface_plan.cpp, fcg_tsi_surface.hip):
+ * 4C's DESIGN THERMO CONVECTION SURF CONDITIONS (a heat transfer coefficient against a surrounding
+ * temperature; 4C_thermo_ele_boundary_impl.cpp, calc_thermo_fextconvection, and
+ * Thermo::TimInt::apply_force_external_conv) and a surface heat flux.  With linear kinematics the
+ * area elements are the reference configuration's and the coefficient is constant per face, so a
+ * surface is a fixed sparse operator on its nodes:
+ *   M_f,ab = sum_g w_g |dA_g| N_a(g) N_b(g),  m_f,a = sum_g w_g |dA_g| N_a(g)   (quad4: 2x2 Gauss,
+ *   quad9: 3x3, the rules and shape functions of fcg_neumann_surface; |dA| = |X,r x X,s|)
+ *   A = sum_f coeff_f M_f,   g = sum_f coeff_f surtemp_f m_f,   q = sum_f flux_f m_f
+ * and per evaluate f_T += s_c (A T - s_t g), K_TT += s_c A; the heat flux load is f_ext += s_q q.
+ * s_c, s_t, s_q: the values at the current time of the condition's time functions.
+ *
+ * fcg_tsi_surface_create: face_nodes[n_faces][4 or 9] are column node ids of tctx in any valid
+ * quad4 / quad9 order (corners cyclic, then mid-edge nodes, then the centre; orientation does not
+ * matter).  A node id outside the column nodes, a node twice in a face, n_faces < 0 or an entry that
+ * the k_TT graph lacks: FCG_ERR_ARG, fcg_tsi_last_error(tctx) names the face.  Works on any context
+ * fcg_tsi_create accepts (hex8 and hex27, any numbering, ranked contexts: pass every face that
+ * touches an owned node; owned rows only are written, columns may be ghosts; a face without an owned
+ * node contributes nothing).  The surface rows are the owned nodes on a face, ascending by thermo
+ * row; each keeps a compact row of the thermo columns of its faces' nodes with the position of every
+ * entry in the k_TT value array.  Blocking.  Destroy the surface before its context.
+ * fcg_tsi_surface_set: the condition's values, each a scalar or a host table per face (a table
+ * takes the scalar's place).  A coefficient that is negative or not finite, a surrounding
+ * temperature or flux that is not finite: FCG_ERR_ARG with the face in *bad_face and in
+ * fcg_tsi_last_error, and the tables of an earlier set stay as they were.  Runs the setup kernel (one
+ * wavefront per surface row, its faces in ascending order, sums in Gauss-point order: no atomics on
+ * doubles, two calls give the same bits); |dA| zero or not finite at a Gauss point: FCG_ERR_SINGULAR
+ * with the lowest failing face index, and the surface counts as not set.  Blocking.
+ * fcg_tsi_convection: one pass over the surface rows, 4 / 16 / 64 lanes per row by the longest
+ * compact row: d_fT_row[row] += s_c (sum_k A_k T[col_k] - s_t g), d_Ktt[pos_k] = fma(s_c, A_k,
+ * d_Ktt[pos_k]).  d_Ktt NULL: residual only (with d_T_col = T_n 4C's explicit Tempn variant);
+ * d_fT_row NULL: tangent only; both NULL, or before a successful set: FCG_ERR_ARG.  Rows that are not
+ * surface rows and entries outside the compact rows are never touched.  Asynchronous on `stream`,
+ * no allocation, deterministic; a surface without rows returns FCG_OK before it looks at its
+ * pointers.  Several surfaces of one context are applied one after the other, each call adds.
+ * fcg_tsi_surface_flux: d_f_row[row] += scale q.  Asynchronous.
+ * fcg_tsi_surface_tables: the device arrays of the surface (rows [n_rows], ptr [n_rows + 1], col /
+ * pos / A [n_entries], g / q [n_rows]), for tests and tools; any pointer may be NULL.
+ */
+typedef struct fcg_tsi_surface fcg_tsi_surface;
+int fcg_tsi_surface_create(fcg_tsi_ctx* tctx, int64_t n_faces, const int32_t* face_nodes,
+    fcg_tsi_surface** out);
+int fcg_tsi_surface_set(fcg_tsi_surface* s, double coeff, const double* face_coeff /* host [n_faces] or NULL */,
+    double surtemp, const double* face_surtemp, double flux, const double* face_flux, int64_t* bad_face);
+int fcg_tsi_surface_info(const fcg_tsi_surface* s, int64_t* n_rows, int64_t* n_entries,
+    int64_t* device_bytes);
+int fcg_tsi_surface_tables(const fcg_tsi_surface* s, const int32_t** d_rows, const int64_t** d_ptr,
+    const int32_t** d_col, const int64_t** d_pos, const double** d_A, const double** d_g,
+    const double** d_q);
+int fcg_tsi_convection(fcg_tsi_surface* s, double coeff_scale, double surtemp_scale,
+    const double* d_T_col, double* d_fT_row /* += , may be NULL */, double* d_Ktt /* += , may be NULL */,
+    void* stream);
+int fcg_tsi_surface_flux(fcg_tsi_surface* s, double scale, double* d_f_row /* += */, void* stream);
+int fcg_tsi_surface_destroy(fcg_tsi_surface* s);
+
+/*
  * Scalar smoothed-aggregation AMG of K_TT (fcg_samg_plan.cpp, fcg_samg.hip): the multigrid of the
  * thermal block, one DOF per node, the constant as near-null space -- what MueLu builds for the
  * thermal field of 4C's TSI block preconditioners, and a solver for a conduction problem on its
